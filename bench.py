@@ -10,6 +10,13 @@ region. Weak scaling: fixed per-GPU batch.
   python bench.py --gpus N --steps K --warmup W        (N>1: launched under torchrun)
 
 Rank 0 prints ONE JSON line; value = whole-job positions/s (max step time over ranks).
+
+A plain run does only what that figure needs: set up, warm up, time the K steps, print the line.
+``--full`` adds the other measurements after (and, for the RCCL probe, before) the timed steps:
+the APV-MCTS sims/s (``mcts_*`` fields; ``--no-mcts`` leaves it out) and, for N>1, the all-reduce
+bandwidth probe (``allreduce_*`` fields). ``--dump-outputs DIR`` writes what the last timed step
+left to its caller (weights, gradients, running loss / accuracy) as ``DIR/<name>.npy``; the
+inputs are seeded, so two builds run with the same arguments can be compared array for array.
 """
 import argparse
 import json
@@ -59,6 +66,33 @@ def allreduce_probe(dp, dev, nbytes=15531176, reps=10):
             "allreduce_ok": ok}
 
 
+DUMP_ARRAY_BYTES = 24 << 20  # per dumped array; three arrays stay well under 64 MB in all
+
+
+def dump_outputs(path, model, trainer):
+    """What the last timed step left to its caller, as float32 ``<path>/<name>.npy``:
+    ``weights`` (the flat fp32 master parameters after the step's SGD update, BatchNorm running
+    statistics included), ``grads`` (the flat fp32 gradients that update consumed) and ``metrics``
+    (the trainer's running sums since the first warmup step: loss sum, hit sum where the model
+    has an accuracy, sample count). An array above DUMP_ARRAY_BYTES is written as a fixed
+    seeded sample of its elements, in index order."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    sums = [trainer.loss_sum]
+    if hasattr(trainer, "metric_acc"):  # the SL trainers keep (loss, hits) of the fused plan here
+        sums = [trainer.loss_sum + trainer.metric_acc[0], trainer.hit_sum + trainer.metric_acc[1]]
+    arrays = {"weights": model.net.flat, "grads": model.net.flat_grad,
+              "metrics": torch.stack([s.detach().float().reshape(()) for s in sums] +
+                                     [torch.tensor(float(trainer.count), device=sums[0].device)])}
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy().reshape(-1)
+        keep = DUMP_ARRAY_BYTES // 4
+        if a.size > keep:
+            a = a[np.sort(np.random.RandomState(20240).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -73,8 +107,14 @@ def main():
     ap.add_argument("--model", default="policy", choices=["policy", "value", "resnet"],
                     help="policy: SL policy net (headline); value: value net (BASELINE config 4); "
                          "resnet: ResnetPolicy SL training (batch-statistics BN)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements: APV-MCTS sims/s after the timed "
+                         "SL steps and, for N>1, the all-reduce bandwidth probe before them")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's results (weights, "
+                         "gradients, metrics) as DIR/<name>.npy")
     ap.add_argument("--no-mcts", action="store_true",
-                    help="skip the APV-MCTS sims/s measurement (run after the timed SL steps)")
+                    help="with --full: skip the APV-MCTS sims/s measurement")
     ap.add_argument("--mcts-playouts", type=int, default=8192)
     ap.add_argument("--mcts-mode", default="master", choices=["master", "shared"],
                     help="N>1 search: one tree on rank 0 whose leaf waves every GPU serves "
@@ -120,7 +160,7 @@ def main():
         if dp.enabled else None
     if dev.type != "cuda":
         raise SystemExit("bench.py needs a GPU")
-    comm = allreduce_probe(dp, dev) if dp.enabled else None
+    comm = allreduce_probe(dp, dev) if dp.enabled and args.full else None
     torch.manual_seed(1234)
     gen = torch.Generator(device=dev)
     gen.manual_seed(99 + dp.rank)
@@ -201,6 +241,9 @@ def main():
     per_rank_ms = [round(float(x) / args.steps * 1e3, 3) for x in rank_t.cpu()]
     ranks_seen = int((rank_t > 0).sum())
     dt = float(rank_t.max())
+    if args.dump_outputs and dp.is_root:
+        # before anything else runs a step: the state is the last timed step's
+        dump_outputs(args.dump_outputs, model, trainer)
     if args.trace:
         # host + device timeline of a few extra (untimed) steps, Chrome-trace JSON
         from torch.profiler import ProfilerActivity, profile
@@ -263,7 +306,7 @@ def main():
         result.update(comm)
     if wd is not None:
         wd.set_phase("mcts", limit_s=max(args.stall_timeout, args.mcts_guard_s + 30))
-    if not args.no_mcts and args.model == "policy":
+    if args.full and not args.no_mcts and args.model == "policy":
         # N = 1: the pipelined single-GPU search. N > 1: ONE search whose leaf waves are dealt
         # to all N GPUs (search/distributed.py) — the whole job's sims/s is that search's.
         # Every rank reaches the all-reduce whether or not its measurement worked (no hang).

@@ -8,9 +8,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-# The reference's own fixtures (SGF games, minimodel.json, Keras HDF5 files) are read in place,
-# never copied: compatibility tests that need them skip when the reference is not mounted.
-REFERENCE_DATA = os.environ.get("RAG_REFERENCE_DATA", "/root/reference/tests/test_data")
+# The reference's data fixtures (SGF games, minimodel.json, Keras HDF5 files) are stored under
+# tests/golden/reference in the reference's own layout (minimodel.json and the dataset's file
+# offsets name paths from its root), so the compatibility tests run from the repository alone.
+REFERENCE_DATA = os.path.join(ROOT, "tests", "golden", "reference", "tests", "test_data")
 
 
 def pytest_configure(config):
@@ -20,8 +21,7 @@ def pytest_configure(config):
 
 @pytest.fixture
 def ref_data():
-    if not os.path.isdir(REFERENCE_DATA):
-        pytest.skip("reference test data not mounted")
+    assert os.path.isdir(REFERENCE_DATA), REFERENCE_DATA + " is missing"
     return REFERENCE_DATA
 
 

@@ -16,6 +16,35 @@ def test_cpu_plumbing_benchmark():
     assert r["status"] == "pass" and r["value"] > 0 and r["n_gpus"] == 0
 
 
+def test_bench_dump_outputs_writes_float32_arrays(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: weights, gradients and the running metric sums as float32 .npy;
+    an array above the per-array limit is the same seeded sample of its elements every time."""
+    from types import SimpleNamespace
+
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    flat = torch.arange(1000, dtype=torch.float32)
+    model = SimpleNamespace(net=SimpleNamespace(flat=flat, flat_grad=-flat))
+    trainer = SimpleNamespace(loss_sum=torch.tensor(1.5), hit_sum=torch.tensor(2.0),
+                              metric_acc=torch.tensor([10.0, 3.0]), count=64)
+    bench.dump_outputs(str(tmp_path / "a"), model, trainer)
+    w = np.load(str(tmp_path / "a" / "weights.npy"))
+    assert w.dtype == np.float32 and np.array_equal(w, flat.numpy())
+    assert np.array_equal(np.load(str(tmp_path / "a" / "grads.npy")), -flat.numpy())
+    assert np.load(str(tmp_path / "a" / "metrics.npy")).tolist() == [11.5, 5.0, 64.0]
+    monkeypatch.setattr(bench, "DUMP_ARRAY_BYTES", 400)
+    del trainer.metric_acc, trainer.hit_sum  # the value trainer: loss sum and count only
+    bench.dump_outputs(str(tmp_path / "b"), model, trainer)
+    bench.dump_outputs(str(tmp_path / "c"), model, trainer)
+    s = np.load(str(tmp_path / "b" / "weights.npy"))
+    assert s.shape == (100,) and np.all(np.diff(s) > 0)
+    assert np.array_equal(s, np.load(str(tmp_path / "c" / "weights.npy")))
+    assert np.array_equal(np.load(str(tmp_path / "b" / "grads.npy")), -s)
+    assert np.load(str(tmp_path / "b" / "metrics.npy")).tolist() == [1.5, 64.0]
+
+
 def test_search_efficiency_effective_from_rows(tmp_path):
     """benchmarks/search_efficiency.py --effective --from-rows: the modelled / effective rates of
     earlier efficiency rows from one GPU's serving rate at (wave, depth), capped by rank 0's

@@ -12,7 +12,8 @@ from rocalphago_amd.features.converter import GameConverter, SizeMismatchError
 from rocalphago_amd.features.preprocessing import DEFAULT_FEATURES
 from rocalphago_amd.io import h5lite, sgf
 
-REF = "/root/reference/tests/test_data"
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference", "tests",
+                   "test_data")
 
 CASES = {
     "plain": "(;GM[1]SZ[9];B[cc];W[gg];B[];W[tt];B[cd])",

@@ -34,7 +34,7 @@ STEPS = {
     "tests": (900, PY + " -m pytest tests -m gpu -x -q --timeout 200 --timeout-method thread",
               "tail2"),
     "smoke": (200, PY + " -c 'import __graft_entry__ as g; g.smoke()'", "tail1"),
-    "bench": (400, PY + " bench.py", "json"),
+    "bench": (400, PY + " bench.py --full", "json"),
     "sl": (200, PY + " bench.py --no-mcts --steps 60 --warmup 10", "json"),
     "sl-long": (300, PY + " bench.py --no-mcts --steps 5000 --warmup 20", "json"),
     "value": (200, PY + " bench.py --model value --no-mcts", "json"),
