@@ -3,6 +3,7 @@
 // index. Replaces the random draw, the symmetry lookup and the two label gathers (four small
 // library kernels per step).
 #include "common.h"
+#include "rag_api.h"
 
 namespace {
 

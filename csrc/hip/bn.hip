@@ -18,6 +18,7 @@
 // All are HBM-bound streaming kernels (one or two reads + one write of a 29 MB activation at
 // B=256, K=128); the conv epilogue does the residual sum of the forward (conv.hip `res`).
 #include "common.h"
+#include "rag_api.h"
 
 using namespace rag;
 

@@ -17,11 +17,10 @@
 // source rows, lane-linear LDS image, swizzle applied on the source address), double-buffered.
 // The MFMA is issued as C^T = W * X^T so each lane owns 4 consecutive output channels of one
 // pixel: the epilogue (bias, ReLU, ReLU-mask, bf16 pack) stores 8 bytes per lane.
-#include <mutex>
-
 #include "common.h"
+#include "conv_host.h"
 #include "pack.h"
-#include "wgrad_part.h"
+#include "rag_api.h"
 
 using namespace rag;
 
@@ -586,14 +585,13 @@ __global__ void pack_nchw_kernel(const float* __restrict__ in, bf16* __restrict_
 }
 
 template <int KS>
-void launch_igemm_ks(int nt, dim3 grid, hipStream_t st, const bf16* X, const bf16* W,
-                     const float* bias, bf16* Y, const bf16* mask, const bf16* res, int M, int S, int WI,
-                     int shift, int WO, int HO, int CIN, int WROWS, int YC, int relu, int HM) {
+void launch_igemm_ks(int nt, dim3 grid, const ConvLaunch& c) {
   switch (nt) {
-#define RAG_NT(N)                                                                              \
-  case N:                                                                                      \
-    conv_igemm_kernel<KS, N><<<grid, 256, 0, st>>>(X, W, bias, Y, mask, res, M, S, WI, shift, WO, \
-                                                   HO, CIN, WROWS, YC, relu, HM);             \
+#define RAG_NT(N)                                                                             \
+  case N:                                                                                     \
+    conv_igemm_kernel<KS, N><<<grid, 256, 0, c.stream>>>(c.x, c.w, c.bias, c.y, c.mask, c.res, \
+                                                         c.M, c.S, c.WI, c.shift, c.WO, c.HO, \
+                                                         c.CIN, c.COUTP, c.YC, c.relu, c.HM); \
     break;
     RAG_NT(1) RAG_NT(2) RAG_NT(3) RAG_NT(4) RAG_NT(6)
 #undef RAG_NT
@@ -611,40 +609,15 @@ int pick_nt(int coutp) {
 }  // namespace
 
 // ============================================================================= C ABI
-bool rag_conv_pipe_launch(const bf16* x, const bf16* w, const float* bias, bf16* y,
-                          const bf16* mk, const bf16* res, int M, int S, int WI, int shift,
-                          int WO, int HO, int CIN, int COUTP, int YC, int KS, int relu, int HM,
-                          hipStream_t stream);  // conv_fwd.hip
-bool rag_conv_tap_launch(const bf16* x, const bf16* w, const float* bias, bf16* y,
-                         const bf16* mk, const bf16* res, int M, int S, int WI, int shift, int WO,
-                         int HO, int CIN, int COUTP, int YC, int KS, int relu, int HM,
-                         long total_rows, hipStream_t stream, const WgradRed* red,
-                         const float* bnc, const float* mcoef, float* spart,
-                         const float* smean);  // conv_tap.hip
-bool rag_conv_tap_bn_ok(int M, int S, int WI, int shift, int CIN, int COUTP, int KS);
-bool rag_wgrad_slab_ok(int S, int H, int HG, int GC, int COUTP, int CINP, int KS);
-
-// Conv forward / dgrad.  X: padded input (halo HI, CIN channels, CIN % 32 == 0).  W: packed
-// bf16 weights [taps][WROWS][CIN].  Y: padded output (halo HO, YC channels, COUTP % 32 == 0,
-// COUTP <= YC).  bias: fp32 [COUTP] or null.  mask: the dgrad ReLU mask (layer input), null or
-// laid out like Y but with its own halo HM.  res: null or a residual added before the activation
-// (ResNet sum-merge), laid out like Y (may alias Y: each element is read then written by one lane).
-// Deferred wgrad reduction (rag_conv_wgrad_deferred): the fp16 partial-slab reduction of one
-// layer waits in a caller-owned handle (PendingRed: the trainer's trunk owns one) and rides along
-// the next conv_tap launch that the caller hands the same handle, on the same stream, as extra
+// Deferred wgrad reduction (rag_conv_wgrad with a `pending` handle): the fp16 partial-slab
+// reduction of one layer waits in a caller-owned handle (PendingRed, conv_host.h: the trainer's
+// trunk owns one) and rides along the next conv_tap launch that the caller hands the same
+// handle, on the same stream, as extra
 // blocks (that launch fills 482 of 512 block slots at B = 256, so the reduction runs in otherwise
 // idle slots instead of as a 14 us kernel of its own). Launches without the handle never see it;
 // a launch with the handle on another stream, a second deferral or rag_wgrad_flush(handle)
 // launches the pending reduction as a standalone kernel. No process-wide state: two trainers (or
 // a trainer and a search) may interleave their launches on one stream.
-int rag_launch_wgrad_slab_reduce(const WgradRed& r, hipStream_t stream);  // wgrad_slab.hip
-struct PendingRed {
-  int valid;
-  hipStream_t stream;
-  WgradRed r;
-  unsigned* dticket;  // the handle's [2] device claim counters (allocated on first deferral)
-};
-
 RAG_API size_t rag_wgrad_pending_bytes() { return sizeof(PendingRed); }
 
 // The handle's claim counters, allocated (and zeroed) when the handle is created rather than on
@@ -688,72 +661,77 @@ RAG_API int rag_wgrad_flush(hipStream_t stream, void* pending) {
   return flush_pending(pending, stream);
 }
 
-// BN prologue fusion (ResnetPolicy): true if rag_conv_igemm_bn / rag_conv_wgrad*_bn can run a
-// layer of this shape with its input given as the BN input x plus [3][S] column coefficients.
+// BN prologue fusion (ResnetPolicy): true if rag_conv_igemm (bnc / mcoef) and rag_conv_wgrad
+// (xcoef) can run a layer of this shape with its input given as the BN input x plus [3][S]
+// column coefficients.
 RAG_API int rag_conv_bn_fusable(int B, int S, int HI, int CIN, int COUTP, int KS) {
   return KS == 3 && HI == 1 && CIN == COUTP &&
          rag_conv_tap_bn_ok(B * S * S, S, S + 2 * HI, HI - 1, CIN, COUTP, KS) &&
          rag_wgrad_slab_ok(S, HI, HI, COUTP, COUTP, CIN, KS);
 }
 
-static int conv_igemm_impl(const void* X, const void* W, const float* bias, void* Y,
-                           const void* mask, const void* resid, int B, int S, int HI, int HO,
-                           int CIN, int COUTP, int YC, int KS, int relu, int HM,
-                           hipStream_t stream, void* pending, const float* bnc,
-                           const float* mcoef, float* spart = nullptr,
-                           const float* smean = nullptr);
-
-namespace {
-// Real input channels of the launch in progress (0 = unknown: the padded CIN is all real);
-// set by rag_conv_igemm_cin for the launch it makes, read by the tap kernels' dispatch.
-}  // namespace
-thread_local int g_conv_cin_real = 0;
-
-// `pending`: null, or the caller's deferred-reduction handle (see PendingRed above).
+// Conv forward / dgrad.  X: padded input (halo HI, CIN channels, CIN % 32 == 0).  W: packed
+// bf16 weights [taps][WROWS][CIN].  Y: padded output (halo HO, YC channels, COUTP % 32 == 0,
+// COUTP <= YC).  bias: fp32 [COUTP] or null.  mask: the dgrad ReLU mask (layer input), null or
+// laid out like Y but with its own halo HM.  res: null or a residual added before the activation
+// (ResNet sum-merge), laid out like Y (may alias Y: each element is read then written by one lane).
+// `pending`: null, or the caller's deferred-reduction handle (see above).
+// cin_real: how many of the CIN (padded) input channels are real, 0 = all: a 5x5 layer with
+// <= 48 of 64 skips the zero channels' MFMAs (conv_tap.hip, PAIR).
+// BN prologue (bnc / mcoef / spart / smean, all optional): X is the BN input x and the layer
+// input is U = ReLU(bnc[0][col] * x + bnc[2][col]) (forward), and/or the dgrad ReLU mask is
+// recomputed from `mask` = x and mcoef (no residual then). spart: the output's BN column
+// statistics as per-block partials [nblk][2][S] for rag_bn_finalize (nblk =
+// rag_conv_bn_stat_blocks); smean: the BN mean for the backward form. -5 if the argument set or
+// the shape has no fused kernel (rag_conv_bn_fusable).
 RAG_API int rag_conv_igemm(const void* X, const void* W, const float* bias, void* Y,
                            const void* mask, const void* resid, int B, int S, int HI, int HO,
                            int CIN, int COUTP, int YC, int KS, int relu, int HM,
-                           hipStream_t stream, void* pending) {
-  return conv_igemm_impl(X, W, bias, Y, mask, resid, B, S, HI, HO, CIN, COUTP, YC, KS, relu, HM,
-                         stream, pending, nullptr, nullptr);
-}
-
-// As rag_conv_igemm, telling the dispatch how many of the CIN (padded) input channels are real:
-// a 5x5 layer with <= 48 of 64 skips the zero channels' MFMAs (conv_tap.hip, PAIR).
-RAG_API int rag_conv_igemm_cin(const void* X, const void* W, const float* bias, void* Y,
-                               const void* mask, const void* resid, int B, int S, int HI, int HO,
-                               int CIN, int COUTP, int YC, int KS, int relu, int HM,
-                               hipStream_t stream, void* pending, int cin_real) {
-  g_conv_cin_real = cin_real;
-  const int rc = conv_igemm_impl(X, W, bias, Y, mask, resid, B, S, HI, HO, CIN, COUTP, YC, KS,
-                                 relu, HM, stream, pending, nullptr, nullptr);
-  g_conv_cin_real = 0;
-  return rc;
-}
-
-// As rag_conv_igemm with the BN prologue: X is the BN input x and the layer input is
-// U = ReLU(bnc[0][col] * x + bnc[2][col]) (forward), and/or the dgrad ReLU mask is recomputed
-// from `mask` = x and mcoef (no residual then). -5 if the shape has no fused kernel
-// (rag_conv_bn_fusable).
-// spart (optional): the output's BN column statistics as per-block partials [nblk][2][S] for
-// rag_bn_finalize (nblk = rag_conv_bn_stat_blocks); smean: the BN mean for the backward form.
-RAG_API int rag_conv_igemm_bn(const void* X, const void* W, const float* bias, void* Y,
-                              const void* mask, const void* resid, int B, int S, int HI, int HO,
-                              int CIN, int COUTP, int YC, int relu, int HM, hipStream_t stream,
-                              void* pending, const float* bnc, const float* mcoef, float* spart,
-                              const float* smean) {
-  if ((!bnc && !mcoef && !spart) || (mcoef && resid) || (smean && !mcoef)) return -5;
-  return conv_igemm_impl(X, W, bias, Y, mask, resid, B, S, HI, HO, CIN, COUTP, YC, 3, relu, HM,
-                         stream, pending, bnc, mcoef, spart, smean);
+                           hipStream_t stream, void* pending, int cin_real, const float* bnc,
+                           const float* mcoef, float* spart, const float* smean) {
+  if ((mcoef && resid) || (smean && !mcoef)) return -5;
+  if (CIN % 32 || COUTP % 32 || YC < COUTP || HI < KS / 2) return -1;
+  const int M = B * S * S;
+  const int WI = S + 2 * HI;
+  ConvLaunch c{(const bf16*)X, (const bf16*)W, bias, (bf16*)Y, (const bf16*)mask,
+               (const bf16*)resid, M, S, WI, HI - KS / 2, S + 2 * HO, HO, CIN, COUTP, YC, KS,
+               relu, HM, (long)B * WI * WI, stream, cin_real, nullptr, bnc, mcoef, spart, smean};
+  WgradRed pend;
+  hipStream_t pend_stream = nullptr;
+  if (take_pending(pending, &pend, &pend_stream)) {
+    if (pend_stream == stream) {
+      c.red = &pend;  // rides along this launch (or goes out on its own just below)
+    } else {
+      const int rc = rag_launch_wgrad_slab_reduce(pend, pend_stream);
+      if (rc) return rc;
+    }
+  }
+  if (rag_conv_tap_launch(c)) return (int)hipGetLastError();
+  if (bnc || mcoef || spart) {  // BN fusion: the 128-channel ping-pong kernel or nothing
+    if (c.red) rag_launch_wgrad_slab_reduce(*c.red, stream);
+    return -5;
+  }
+  if (c.red) {  // not a tap-slab launch: the reduction goes out on its own first
+    const int rc = rag_launch_wgrad_slab_reduce(*c.red, stream);
+    if (rc) return rc;
+  }
+  if (rag_conv_pipe_launch(c)) return (int)hipGetLastError();
+  const int nt = pick_nt(COUTP);
+  const dim3 grid((M + kBM - 1) / kBM, COUTP / (32 * nt));
+  switch (KS) {
+    case 1: launch_igemm_ks<1>(nt, grid, c); break;
+    case 3: launch_igemm_ks<3>(nt, grid, c); break;
+    case 5: launch_igemm_ks<5>(nt, grid, c); break;
+    case 7: launch_igemm_ks<7>(nt, grid, c); break;
+    default: return -2;
+  }
+  return (int)hipGetLastError();
 }
 
 // Winograd F(2,3) 3x3 convolution (conv_wino.hip): forward or dgrad with the layer's Winograd
 // weights [12][NOUT][KIN] (rag_wino_pack). A deferred wgrad reduction in `pending` rides along
 // the launch (every block claims units of it after its epilogue) when it has claim counters and
 // the grid is one-dimensional; otherwise it goes out on its own first.
-int rag_conv_wino_launch(const void* X, const void* W, const float* bias, void* Y,
-                         const void* mask, int B, int S, int KIN, int NOUT, int HO, int YC,
-                         int relu, int HM, hipStream_t stream, const WgradRed* red, int half);
 // The pending reduction of `pending` for a Winograd launch of NOUT channels on `stream`: it rides
 // (returned in *pend, *red = pend) when it has claim counters and the grid is one-dimensional,
 // else it goes out on its own now. Returns that launch's error code (0).
@@ -769,9 +747,10 @@ static int wino_pending(void* pending, hipStream_t stream, int NOUT, WgradRed* p
   return rag_launch_wgrad_slab_reduce(*pend, pend_stream);
 }
 
-RAG_API int rag_conv_wino_p(const void* X, const void* W, const float* bias, void* Y,
-                            const void* mask, int B, int S, int KIN, int NOUT, int HO, int YC,
-                            int relu, int HM, hipStream_t stream, void* pending, int half) {
+// half: see rag_conv_wino_launch (conv_wino.hip).
+RAG_API int rag_conv_wino(const void* X, const void* W, const float* bias, void* Y,
+                          const void* mask, int B, int S, int KIN, int NOUT, int HO, int YC,
+                          int relu, int HM, hipStream_t stream, void* pending, int half) {
   WgradRed pend;
   const WgradRed* red = nullptr;
   if (const int rc = wino_pending(pending, stream, NOUT, &pend, &red)) return rc;
@@ -784,12 +763,6 @@ RAG_API int rag_conv_wino_p(const void* X, const void* W, const float* bias, voi
 // transform; `resid` optional) or dgrad with `mcoef` (mask = x); `spart` [B][2][S] per-board
 // column statistics (forward: sum y, sum y^2; dgrad with smean: sum dU, sum dU (x - mean)).
 // -5 when rag_conv_wino_bn_ok is false for the shape or the argument set has no kernel.
-int rag_conv_wino_bn_launch(const void* X, const void* W, const float* bias, void* Y,
-                            const void* mask, const void* res, int B, int S, int KIN, int NOUT,
-                            int HO, int YC, int relu, int HM, hipStream_t stream,
-                            const WgradRed* red, const float* coef, const float* mcoef,
-                            float* spart, const float* smean);
-RAG_API int rag_conv_wino_bn_ok(int B, int S, int KIN, int NOUT);
 RAG_API int rag_conv_wino_bn(const void* X, const void* W, const float* bias, void* Y,
                              const void* mask, const void* resid, int B, int S, int KIN, int NOUT,
                              int HO, int YC, int relu, int HM, hipStream_t stream, void* pending,
@@ -805,82 +778,10 @@ RAG_API int rag_conv_wino_bn(const void* X, const void* W, const float* bias, vo
                                  stream, red, coef, mcoef, spart, smean);
 }
 
-// Partial rows rag_conv_igemm_bn writes to `spart` (one per convolution block).
+// Partial rows rag_conv_igemm writes to `spart` (one per convolution block).
 RAG_API int rag_conv_bn_stat_blocks(int B, int S, int COUTP) {
   return ((B * S * S + 383) / 384) * (COUTP / 128);
 }
-
-static int conv_igemm_impl(const void* X, const void* W, const float* bias, void* Y,
-                           const void* mask, const void* resid, int B, int S, int HI, int HO,
-                           int CIN, int COUTP, int YC, int KS, int relu, int HM,
-                           hipStream_t stream, void* pending, const float* bnc,
-                           const float* mcoef, float* spart, const float* smean) {
-  if (CIN % 32 || COUTP % 32 || YC < COUTP || HI < KS / 2) return -1;
-  const int M = B * S * S;
-  const int nt = pick_nt(COUTP);
-  dim3 grid((M + kBM - 1) / kBM, COUTP / (32 * nt));
-  const int WI = S + 2 * HI, WO = S + 2 * HO, shift = HI - KS / 2;
-  const bf16* x = (const bf16*)X;
-  const bf16* w = (const bf16*)W;
-  bf16* y = (bf16*)Y;
-  const bf16* mk = (const bf16*)mask;
-  const bf16* res = (const bf16*)resid;
-  WgradRed pend;
-  hipStream_t pend_stream = nullptr;
-  const WgradRed* red = nullptr;
-  if (take_pending(pending, &pend, &pend_stream)) {
-    if (pend_stream == stream) {
-      red = &pend;  // rides along this launch (or goes out on its own just below)
-    } else {
-      const int rc = rag_launch_wgrad_slab_reduce(pend, pend_stream);
-      if (rc) return rc;
-    }
-  }
-  if (bnc || mcoef || spart) {  // BN fusion: the 128-channel ping-pong kernel or nothing
-    if (rag_conv_tap_launch(x, w, bias, y, mk, res, M, S, WI, shift, WO, HO, CIN, COUTP, YC, KS,
-                            relu, HM, (long)B * WI * WI, stream, red, bnc, mcoef, spart, smean))
-      return (int)hipGetLastError();
-    if (red) rag_launch_wgrad_slab_reduce(*red, stream);
-    return -5;
-  }
-  if (rag_conv_tap_launch(x, w, bias, y, mk, res, M, S, WI, shift, WO, HO, CIN,
-                                      COUTP, YC, KS, relu, HM, (long)B * WI * WI, stream, red,
-                                      nullptr, nullptr, nullptr, nullptr))
-    return (int)hipGetLastError();
-  if (red) {  // not a tap-slab launch: the reduction goes out on its own first
-    const int rc = rag_launch_wgrad_slab_reduce(*red, stream);
-    if (rc) return rc;
-  }
-  if (rag_conv_pipe_launch(x, w, bias, y, mk, res, M, S, WI, shift, WO, HO, CIN,
-                                       COUTP, YC, KS, relu, HM, stream))
-    return (int)hipGetLastError();
-  switch (KS) {
-    case 1: launch_igemm_ks<1>(nt, grid, stream, x, w, bias, y, mk, res, M, S, WI, shift, WO, HO, CIN, COUTP, YC, relu, HM); break;
-    case 3: launch_igemm_ks<3>(nt, grid, stream, x, w, bias, y, mk, res, M, S, WI, shift, WO, HO, CIN, COUTP, YC, relu, HM); break;
-    case 5: launch_igemm_ks<5>(nt, grid, stream, x, w, bias, y, mk, res, M, S, WI, shift, WO, HO, CIN, COUTP, YC, relu, HM); break;
-    case 7: launch_igemm_ks<7>(nt, grid, stream, x, w, bias, y, mk, res, M, S, WI, shift, WO, HO, CIN, COUTP, YC, relu, HM); break;
-    default: return -2;
-  }
-  return (int)hipGetLastError();
-}
-
-// Workspace (floats) needed by rag_conv_wgrad for the partial slabs.
-int rag_launch_wgrad_taps(const bf16* G, const bf16* X, float* part, float* bpart, int R, int WP,
-                          int GC, int CIN, int spc, int COUTP, int CINP, int KS, int RG,
-                          int nchunks, hipStream_t stream);  // wgrad.hip
-bool rag_wgrad_taps_fits(int WP, int KS, int RG);  // wgrad.hip
-int rag_wgrad_taps_target_blocks();  // wgrad.hip
-bool rag_wgrad_slab_ok(int S, int H, int HG, int GC, int COUTP, int CINP, int KS);  // wgrad_slab.hip
-int rag_wgrad_slab_nchunks(int R, int CINP, int* spc, int KS, int pair5 = 0);     // wgrad_slab.hip
-bool rag_wgrad_slab_bf16();                                                        // wgrad_slab.hip
-WgradRed rag_wgrad_slab_red(const void* part, const float* bpart, float* dW, float* db,
-                            int nchunks, int CINP, int COUTP, int COUT, int CIN, int accumulate,
-                            int KS, int pair5);
-int rag_launch_wgrad_slab_reduce(const WgradRed& r, hipStream_t stream);        // wgrad_slab.hip
-int rag_launch_wgrad_slab(const bf16* G, const bf16* X, float* part, float* bpart, int R, int WP,
-                          int GC, int CIN, int spc, int CINP, int nchunks, hipStream_t stream,
-                          const float* xcoef, int S, int KS, int COUTP, int pair5,
-                          unsigned* ticket_reset);
 
 namespace {
 // all-taps variant applicability and plan (see wgrad.hip)
@@ -959,11 +860,16 @@ static void launch_wgrad_ks(int ntn, int ntc, dim3 grid, hipStream_t st, const b
 
 // Weight + bias gradient. G: dL/d(pre-activation) in padded layout (halo 1, GC channels).
 // X: the layer input (halo HI, CINP channels). dW: OIHW fp32 [COUT][CIN][KS][KS]. db: [COUT].
-static int conv_wgrad_impl(const void* G, const void* X, float* dW, float* db, float* work,
+// pending: null reduces at once; a handle leaves an fp16 partial-slab reduction pending in it for
+// the next conv launch given that handle on `stream`: dW / db are complete once that launch (or
+// rag_wgrad_flush(handle)) ran. A reduction already pending in the handle is launched first; -4
+// for a handle without claim counters (rag_wgrad_pending_init).
+// xcoef (BN prologue, optional): X is the BN input x and the layer input is
+// U = ReLU(xcoef[0][col] * x + xcoef[2][col]) (-5 if the shape has no fused kernel).
+RAG_API int rag_conv_wgrad(const void* G, const void* X, float* dW, float* db, float* work,
                            int B, int S, int HI, int HG, int GC, int COUT, int COUTP, int CIN,
-                           int CINP, int KS, int accumulate, hipStream_t stream,
-                           hipStream_t reduce_stream, void* pending,
-                           const float* xcoef = nullptr) {
+                           int CINP, int KS, int accumulate, hipStream_t stream, void* pending,
+                           const float* xcoef) {
   {  // a pending reduction reads the partial slabs this wgrad is about to overwrite
     const int rc = flush_pending(pending, nullptr);
     if (rc) return rc;
@@ -993,10 +899,9 @@ static int conv_wgrad_impl(const void* G, const void* X, float* dW, float* db, f
     // a reduction deferred on this stream gets claim counters, zeroed by this launch (so a
     // claiming launch that ended early cannot leave the next one a stale ticket)
     unsigned* ticket_reset = nullptr;
-    if (defer && bf16_part && !(reduce_stream && reduce_stream != stream)) {
-      PendingRed* p = static_cast<PendingRed*>(pending);
-      if (!p->dticket && hipMalloc(&p->dticket, 2 * sizeof(unsigned)) != hipSuccess) return -3;
-      ticket_reset = p->dticket;
+    if (defer && bf16_part) {
+      ticket_reset = static_cast<PendingRed*>(pending)->dticket;
+      if (!ticket_reset) return -4;
     }
     const int rc = rag_launch_wgrad_slab(g, x, part, bpart, R, WP, GC, CINP, spc, CINP, nchunks,
                                          stream, xcoef, S, KS, COUTP, pair5, ticket_reset);
@@ -1027,23 +932,10 @@ static int conv_wgrad_impl(const void* G, const void* X, float* dW, float* db, f
       default: return -2;
     }
   }
-  // The slab reduce is bandwidth-bound while the next kernels (dgrad) are MFMA-bound: with a
-  // separate reduce stream it runs concurrently with them, ordered after this wgrad by an event.
-  hipStream_t rs = stream;
-  if (reduce_stream && reduce_stream != stream) {
-    static hipEvent_t ring[16];
-    static int next = 0;
-    hipEvent_t& ev = ring[next];
-    next = (next + 1) & 15;
-    if (!ev && hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return -3;
-    if (hipEventRecord(ev, stream) != hipSuccess) return -3;
-    if (hipStreamWaitEvent(reduce_stream, ev, 0) != hipSuccess) return -3;
-    rs = reduce_stream;
-  }
   if (bf16_part) {
     const WgradRed r = rag_wgrad_slab_red(part, bpart, dW, db, nchunks, CINP, COUTP, COUT, CIN,
                                           accumulate, KS, slab ? pair5 : 0);
-    if (defer && rs == stream) {
+    if (defer) {
       PendingRed* p = static_cast<PendingRed*>(pending);
       p->r = r;
       // the riding reduce blocks claim units dynamically (launches that keep the static split
@@ -1053,44 +945,13 @@ static int conv_wgrad_impl(const void* G, const void* X, float* dW, float* db, f
       p->valid = 1;
       return 0;
     }
-    return rag_launch_wgrad_slab_reduce(r, rs);
+    return rag_launch_wgrad_slab_reduce(r, stream);
   }
   const int total = taps * COUTP * CINP / 4 + COUTP;
   const int blocks = (total + 255) / 256;  // 4 chunk loads in flight per thread (8 / 16: same)
-  wgrad_reduce_kernel<4><<<blocks, 256, 0, rs>>>(part, bpart, dW, db, nchunks, taps, COUT, CIN,
-                                                 COUTP, CINP, KS, accumulate);
+  wgrad_reduce_kernel<4><<<blocks, 256, 0, stream>>>(part, bpart, dW, db, nchunks, taps, COUT,
+                                                     CIN, COUTP, CINP, KS, accumulate);
   return (int)hipGetLastError();
-}
-
-RAG_API int rag_conv_wgrad(const void* G, const void* X, float* dW, float* db, float* work,
-                           int B, int S, int HI, int HG, int GC, int COUT, int COUTP, int CIN,
-                           int CINP, int KS, int accumulate, hipStream_t stream,
-                           hipStream_t reduce_stream) {
-  return conv_wgrad_impl(G, X, dW, db, work, B, S, HI, HG, GC, COUT, COUTP, CIN, CINP, KS,
-                         accumulate, stream, reduce_stream, nullptr);
-}
-
-// As rag_conv_wgrad, but an fp16 partial-slab reduction is left pending in the caller's handle
-// for the next conv launch given that handle on `stream`; dW / db are complete once that launch
-// (or rag_wgrad_flush(handle)) ran. A reduction already pending in the handle is launched first.
-RAG_API int rag_conv_wgrad_deferred(const void* G, const void* X, float* dW, float* db,
-                                    float* work, int B, int S, int HI, int HG, int GC, int COUT,
-                                    int COUTP, int CIN, int CINP, int KS, int accumulate,
-                                    hipStream_t stream, void* pending) {
-  if (!pending) return -4;
-  return conv_wgrad_impl(G, X, dW, db, work, B, S, HI, HG, GC, COUT, COUTP, CIN, CINP, KS,
-                         accumulate, stream, nullptr, pending);
-}
-
-// As rag_conv_wgrad_deferred with the BN prologue: X is the BN input x and the layer input is
-// U = ReLU(xcoef[0][col] * x + xcoef[2][col]) (-5 if the shape has no fused kernel).
-RAG_API int rag_conv_wgrad_deferred_bn(const void* G, const void* X, float* dW, float* db,
-                                       float* work, int B, int S, int HI, int HG, int GC, int COUT,
-                                       int COUTP, int CIN, int CINP, int KS, int accumulate,
-                                       hipStream_t stream, void* pending, const float* xcoef) {
-  if (!xcoef) return -5;
-  return conv_wgrad_impl(G, X, dW, db, work, B, S, HI, HG, GC, COUT, COUTP, CIN, CINP, KS,
-                         accumulate, stream, nullptr, pending, xcoef);
 }
 
 RAG_API int rag_pack_weights(const float* W, void* Wf, void* Wb, int COUT, int CIN, int KS,

@@ -16,6 +16,7 @@
 // owns 64 x BN/2 and issues 4 x BN/32 MFMA 16x16x32 per K-step. 60 KB of LDS per block -> two
 // blocks per CU.
 #include "common.h"
+#include "conv_host.h"
 
 using namespace rag;
 
@@ -23,9 +24,9 @@ namespace {
 
 constexpr int kBK = 32;
 constexpr int kNBUF = 3;
-// K-loop order: 0 = tap outer / channel chunk inner (A/B, rag_conv_order), 1 (default: 3-8 %
-// faster) = channel chunk outer / tap inner
-int g_conv_order = 1;
+// K-loop order (a kernel argument): 0 = tap outer / channel chunk inner, 1 (3-8 % faster, what
+// every launch passes) = channel chunk outer / tap inner
+constexpr int kConvOrder = 1;
 
 template <int KS, int NT, int MT>
 __global__ void __launch_bounds__(256, 2)
@@ -213,14 +214,13 @@ conv_pipe_kernel(const bf16* __restrict__ X, const bf16* __restrict__ Wt,
 }
 
 template <int KS>
-bool launch_ks(int nt, int mt, dim3 grid, hipStream_t st, const bf16* X, const bf16* W,
-               const float* bias, bf16* Y, const bf16* mask, const bf16* res, int M, int S,
-               int WI, int shift, int WO, int HO, int CIN, int WROWS, int YC, int relu, int HM) {
+bool launch_ks(int nt, int mt, dim3 grid, const ConvLaunch& c) {
 #define RAG_PIPE(N, T)                                                                        \
   if (nt == N && mt == T) {                                                                   \
-    conv_pipe_kernel<KS, N, T><<<grid, 256, 0, st>>>(X, W, bias, Y, mask, res, M, S, WI,    \
-                                                         shift, WO, HO, CIN, WROWS, YC, relu,  \
-                                                         HM, g_conv_order);                    \
+    conv_pipe_kernel<KS, N, T><<<grid, 256, 0, c.stream>>>(c.x, c.w, c.bias, c.y, c.mask,    \
+                                                           c.res, c.M, c.S, c.WI, c.shift,    \
+                                                           c.WO, c.HO, c.CIN, c.COUTP, c.YC,  \
+                                                           c.relu, c.HM, kConvOrder);         \
     return true;                                                                              \
   }
   RAG_PIPE(2, 4) RAG_PIPE(2, 6) RAG_PIPE(2, 8) RAG_PIPE(4, 4)
@@ -257,28 +257,19 @@ int pick_mt(int M, int nt, int ntiles_n) {
 
 // Returns true if the pipelined kernel handled the launch (COUTP multiple of 64; any KS in
 // {1,3,5,7}); false leaves it to the generic kernel in conv.hip.
-bool rag_conv_pipe_launch(const bf16* x, const bf16* w, const float* bias, bf16* y,
-                          const bf16* mk, const bf16* res, int M, int S, int WI, int shift,
-                          int WO, int HO, int CIN, int COUTP, int YC, int KS, int relu, int HM, hipStream_t stream) {
-  const int nt = COUTP % 192 == 0 ? 6 : (COUTP % 128 == 0 ? 4 : (COUTP % 64 == 0 ? 2 : 0));
+bool rag_conv_pipe_launch(const ConvLaunch& c) {
+  const int nt = c.COUTP % 192 == 0 ? 6 : (c.COUTP % 128 == 0 ? 4 : (c.COUTP % 64 == 0 ? 2 : 0));
   if (!nt) return false;
-  const int ntn = COUTP / (32 * nt);
-  const int mt = pick_mt(M, nt, ntn);
+  const int ntn = c.COUTP / (32 * nt);
+  const int mt = pick_mt(c.M, nt, ntn);
   const int bm = 32 * mt;
-  const int nblk_m = (M + bm - 1) / bm;
+  const int nblk_m = (c.M + bm - 1) / bm;
   dim3 grid(nblk_m * ntn);
-  switch (KS) {
-    case 1: return launch_ks<1>(nt, mt, grid, stream, x, w, bias, y, mk, res, M, S, WI, shift, WO, HO, CIN, COUTP, YC, relu, HM);
-    case 3: return launch_ks<3>(nt, mt, grid, stream, x, w, bias, y, mk, res, M, S, WI, shift, WO, HO, CIN, COUTP, YC, relu, HM);
-    case 5: return launch_ks<5>(nt, mt, grid, stream, x, w, bias, y, mk, res, M, S, WI, shift, WO, HO, CIN, COUTP, YC, relu, HM);
-    case 7: return launch_ks<7>(nt, mt, grid, stream, x, w, bias, y, mk, res, M, S, WI, shift, WO, HO, CIN, COUTP, YC, relu, HM);
+  switch (c.KS) {
+    case 1: return launch_ks<1>(nt, mt, grid, c);
+    case 3: return launch_ks<3>(nt, mt, grid, c);
+    case 5: return launch_ks<5>(nt, mt, grid, c);
+    case 7: return launch_ks<7>(nt, mt, grid, c);
     default: return false;
   }
-}
-
-// K-loop order of conv_pipe (see g_conv_order); returns the previous setting.
-RAG_API int rag_conv_order(int order) {
-  const int old = g_conv_order;
-  g_conv_order = order;
-  return old;
 }

@@ -18,13 +18,13 @@
 //     `s_waitcnt vmcnt(N)` (each wave issues 3 weight and 5 slab loads) + raw s_barrier.
 // LDS: 2 x 20 KB + 3 x 12 KB = 76 KB -> two blocks per CU, like conv_pipe.
 #include <algorithm>
+#include <atomic>
 
 #include "common.h"
-#include "wgrad_part.h"
+#include "conv_host.h"
+#include "rag_api.h"
 
 using namespace rag;
-
-extern thread_local int g_conv_cin_real;  // conv.hip: real input channels of this launch
 
 namespace {
 
@@ -828,36 +828,48 @@ conv_tap_pp_kernel(const bf16* __restrict__ X, const bf16* __restrict__ Wt,
   }
 }
 
-// Dispatch mode (RAG_CONV_TAP / rag_conv_tap_mode, read on first use): 0 = none of these kernels
+// Dispatch mode (RAG_CONV_TAP, read on first use; rag_conv_tap_mode sets it for the A/B test of
+// mode 6 against 12, tests/test_resnet_gpu.py): 0 = none of these kernels
 // (conv_pipe / the caller's fallback), 6 = the plain ping-pong kernel (round 3: all slab loads at
 // tap 0, per-segment priority flips) as the A/B alternative, 12 (default) = slab loads spread
 // over a chunk's taps + one static priority for the second wave group: SL 111.7-111.9k ->
 // 113.6-113.9k positions/s on one box (profiles/conv_variants_r4b.txt). The 128-wide, 5x5 and
 // sub-chip kernels are the same in both modes.
-int g_tap_mode = -1;
+std::atomic<int> g_tap_mode{-1};  // < 0: not read yet
+int tap_mode() {
+  int mode = g_tap_mode.load(std::memory_order_relaxed);
+  if (mode < 0) {
+    const char* e = getenv("RAG_CONV_TAP");
+    const int env = e ? atoi(e) : 12;
+    g_tap_mode.compare_exchange_strong(mode, env);  // (a concurrent setter's value wins)
+    if (mode < 0) mode = env;
+  }
+  return mode;
+}
 // Fewer 384-pixel blocks than this leave most of the chip idle: the 192-pixel kernels run them
 // (B = 256 at 19x19 is 241 blocks and stays on the 384-pixel kernel).
 constexpr int kPPMinBlocks = 200;
 
-// Worst-case slab extent of a bm-pixel run (host check of the kernels' slab-row assumptions).
-int max_slab_rows(int S, int WI, int shift, int bm, int KS = 3) {
+// Worst-case slab extent of a BM-pixel run of a KS x KS layer (host check of the kernels'
+// slab-row assumptions). The last geometry is cached per thread and (BM, KS): a trunk's
+// launches repeat one, and launches may come from several threads at once.
+template <int BM, int KS>
+int max_slab_rows(int S, int WI, int shift) {
+  struct Entry {
+    int S, WI, shift, rows;
+  };
+  thread_local Entry e{-1, 0, 0, 0};
+  if (e.S == S && e.WI == WI && e.shift == shift) return e.rows;
   const int S2 = S * S;
   auto prow = [&](long m) {
     const long b = m / S2, rem = m - b * S2, i = rem / S, j = rem - i * S;
     return (b * WI + i + shift) * WI + j + shift;
   };
   long mx = 0;
-  for (long m0 = 0; m0 < (long)S2 * bm + bm; m0 += bm)
-    mx = std::max(mx, prow(m0 + bm - 1) + (KS - 1) * (WI + 1) - prow(m0) + 1);
-  return (int)mx;
-}
-
-int tap_mode() {
-  if (g_tap_mode < 0) {
-    const char* e = getenv("RAG_CONV_TAP");
-    g_tap_mode = e ? atoi(e) : 12;
-  }
-  return g_tap_mode;
+  for (long m0 = 0; m0 < (long)S2 * BM + BM; m0 += BM)
+    mx = std::max(mx, prow(m0 + BM - 1) + (KS - 1) * (WI + 1) - prow(m0) + 1);
+  e = Entry{S, WI, shift, (int)mx};
+  return e.rows;
 }
 
 // The reduce-block slots a launch of `nconv` one-per-CU blocks leaves free on 256 CUs (>= 8),
@@ -871,17 +883,8 @@ int reduce_slots(int nconv, const WgradRed* red, WgradRed& r, bool claim) {
 }
 }  // namespace
 
-RAG_API int rag_conv_tap_mode(int mode) {
-  const int old = g_tap_mode;
-  g_tap_mode = mode;
-  return old;
-}
-
-int rag_launch_wgrad_slab_reduce(const WgradRed& r, hipStream_t stream);  // wgrad_slab.hip
-
-// bnc / mcoef (BN prologue / mask coefficients, conv_tap_pp_kernel BNP): only the 128-channel
-// ping-pong path takes them; with either set, any other shape returns false.
-bool rag_conv_tap_bn_ok(int M, int S, int WI, int shift, int CIN, int COUTP, int KS);
+// Sets the dispatch mode (< 0: back to RAG_CONV_TAP / the default); returns the previous setting.
+RAG_API int rag_conv_tap_mode(int mode) { return g_tap_mode.exchange(mode); }
 
 // Returns true if one of this file's kernels handled the launch: 3x3 or 5x5, 192- or
 // 128-multiple output channels, input channels a multiple of 32, and every pixel run's tap
@@ -889,45 +892,41 @@ bool rag_conv_tap_bn_ok(int M, int S, int WI, int shift, int CIN, int COUTP, int
 // (3x3 192: default / plain A/B; 128: with or without the BN prologue; 5x5: tap-paired input
 // layer or plain) when the grid fills the chip, else its 192-pixel form (MT = 3), else (3x3 192,
 // small grids) the 4-wave conv_tap_kernel.
-bool rag_conv_tap_launch(const bf16* x, const bf16* w, const float* bias, bf16* y,
-                         const bf16* mk, const bf16* res, int M, int S, int WI, int shift, int WO,
-                         int HO, int CIN, int COUTP, int YC, int KS, int relu, int HM, long total_rows,
-                         hipStream_t stream, const WgradRed* red, const float* bnc,
-                         const float* mcoef, float* spart, const float* smean) {
-  if ((bnc || mcoef || spart) &&
-      ((mcoef && res) || !rag_conv_tap_bn_ok(M, S, WI, shift, CIN, COUTP, KS)))
+// bnc / mcoef / spart (BN prologue / mask coefficients / statistics, conv_tap_pp_kernel BNP):
+// only the 128-channel ping-pong path takes them; with any set, any other shape returns false.
+bool rag_conv_tap_launch(const ConvLaunch& c) {
+  const bool bn = c.bnc || c.mcoef || c.spart;
+  if (bn && ((c.mcoef && c.res) ||
+             !rag_conv_tap_bn_ok(c.M, c.S, c.WI, c.shift, c.CIN, c.COUTP, c.KS)))
     return false;
   const int mode = tap_mode();
+  const int M = c.M, COUTP = c.COUTP;
   // 192-multiple widths: 96 x 96 wave tiles (NT = 6); 128-multiple widths (ResnetPolicy's and
   // the reference CNNPolicy's default 128 filters) only on the ping-pong kernel, 96 x 64 (NT = 4)
   const bool w192 = COUTP % kBN == 0, w128 = !w192 && COUTP % 128 == 0;
-  if (!mode || !(KS == 3 || KS == 5) || !(w192 || w128) || CIN % kBK || CIN < kBK) return false;
+  if (!mode || !(c.KS == 3 || c.KS == 5) || !(w192 || w128) || c.CIN % kBK || c.CIN < kBK)
+    return false;
+  hipStream_t stream = c.stream;
   WgradRed r{};
-#define RAG_PP_ARGS(NCONV)                                                                      \
-  x, w, bias, y, mk, res, M, S, WI, shift, WO, HO, CIN, COUTP, YC, relu, HM, total_rows, NCONV, r
-  if (KS == 5) {
+#define RAG_PP_ARGS(NCONV)                                                                   \
+  c.x, c.w, c.bias, c.y, c.mask, c.res, M, c.S, c.WI, c.shift, c.WO, c.HO, c.CIN, COUTP, c.YC, \
+      c.relu, c.HM, c.total_rows, NCONV, r
+  if (c.KS == 5) {
     // 5x5 (the SL input layer, ResnetPolicy's first unit): the ping-pong kernel over 25 taps,
     // when the grid fills the chip and every 384-pixel run's 25-tap slab fits 768 rows
-    static int key5 = -1, rows5 = 0, rows5b = 0;
-    const int k5 = S * 4096 + WI * 8 + shift;
-    if (k5 != key5) {
-      rows5 = max_slab_rows(S, WI, shift, kPPBM, KS);
-      rows5b = max_slab_rows(S, WI, shift, kBM, KS);
-      key5 = k5;
-    }
-    if (bnc || mcoef || spart) return false;
+    if (bn) return false;
     const int nconv = ((M + kPPBM - 1) / kPPBM) * (COUTP / (w192 ? kBN : 128));
-    // <= 48 real input channels in a 64-channel layout (the caller's hint, rag_conv_igemm_cin):
-    // chunk 1 steps pair two taps
-    const bool pair5 = CIN == 64 && g_conv_cin_real > 0 && g_conv_cin_real <= 48;
+    // <= 48 real input channels in a 64-channel layout (the caller's hint, cin_real): chunk 1
+    // steps pair two taps
+    const bool pair5 = c.CIN == 64 && c.cin_real > 0 && c.cin_real <= 48;
     if (nconv < kPPMinBlocks) {
       // sub-chip grids (128-game self-play passes): 192-pixel blocks, as the 3x3 layers, at
       // every such batch (a block's time is the launch's: the self-play tail's plies of < 107
       // games ran conv_pipe at 45.6 us against 32.5 us for this kernel at 128 games,
       // profiles/rl_selfplay_r5.txt)
       const int n192 = ((M + kBM - 1) / kBM) * (COUTP / kBN);
-      if (!w192 || rows5b > kPPSlabRows192x5) return false;
-      const int nred = reduce_slots(n192, red, r, false);
+      if (!w192 || max_slab_rows<kBM, 5>(c.S, c.WI, c.shift) > kPPSlabRows192x5) return false;
+      const int nred = reduce_slots(n192, c.red, r, false);
       if (pair5)
         conv_tap_pp_kernel<3, 6, false, 5, 3, 0, 0, 1><<<n192 + nred, 512, 0, stream>>>(
             RAG_PP_ARGS(n192));
@@ -935,8 +934,8 @@ bool rag_conv_tap_launch(const bf16* x, const bf16* w, const float* bias, bf16* 
         conv_tap_pp_kernel<3, 6, false, 5, 3><<<n192 + nred, 512, 0, stream>>>(RAG_PP_ARGS(n192));
       return true;
     }
-    if (rows5 > kPPSlabRows5) return false;
-    const int nred = reduce_slots(nconv, red, r, !w192);
+    if (max_slab_rows<kPPBM, 5>(c.S, c.WI, c.shift) > kPPSlabRows5) return false;
+    const int nred = reduce_slots(nconv, c.red, r, !w192);
     if (w192 && pair5)
       conv_tap_pp_kernel<3, 6, false, 5, kMT, 0, 0, 1><<<nconv + nred, 512, 0, stream>>>(
           RAG_PP_ARGS(nconv));
@@ -949,30 +948,24 @@ bool rag_conv_tap_launch(const bf16* x, const bf16* w, const float* bias, bf16* 
       conv_tap_pp_kernel<3, 4, false, 5><<<nconv + nred, 512, 0, stream>>>(RAG_PP_ARGS(nconv));
     return true;
   }
-  static int cached_key = -1, cached_rows = 0, cached_rows8 = 0;
-  const int key = S * 4096 + WI * 8 + shift;
-  if (key != cached_key) {
-    cached_rows = max_slab_rows(S, WI, shift, kBM);
-    cached_rows8 = max_slab_rows(S, WI, shift, kPPBM);
-    cached_key = key;
-  }
+  const int rows384 = max_slab_rows<kPPBM, 3>(c.S, c.WI, c.shift);
   if (w128) {
     const int nconv = ((M + kPPBM - 1) / kPPBM) * (COUTP / 128);
-    if (cached_rows8 > kPPSlabRows || nconv < kPPMinBlocks) return false;  // small: conv_pipe
+    if (rows384 > kPPSlabRows || nconv < kPPMinBlocks) return false;  // small: conv_pipe
     // claimed reduction (r.ticket): CNNPolicy-128 164.9 -> 169.2 k positions/s
-    const int nred = reduce_slots(nconv, red, r, true);
-    if (bnc)
-      conv_tap_pp_kernel<3, 4, true><<<nconv + nred, 512, 0, stream>>>(RAG_PP_ARGS(nconv), bnc,
-                                                                        mcoef, spart, smean);
+    const int nred = reduce_slots(nconv, c.red, r, true);
+    if (c.bnc)
+      conv_tap_pp_kernel<3, 4, true><<<nconv + nred, 512, 0, stream>>>(
+          RAG_PP_ARGS(nconv), c.bnc, c.mcoef, c.spart, c.smean);
     else
       conv_tap_pp_kernel<3, 4, false><<<nconv + nred, 512, 0, stream>>>(
-          RAG_PP_ARGS(nconv), nullptr, mcoef, spart, smean);
+          RAG_PP_ARGS(nconv), nullptr, c.mcoef, c.spart, c.smean);
     return true;
   }
   const int nconv = ((M + kPPBM - 1) / kPPBM) * (COUTP / kBN);
-  if (cached_rows8 <= kPPSlabRows && nconv >= kPPMinBlocks) {
+  if (rows384 <= kPPSlabRows && nconv >= kPPMinBlocks) {
     // ping-pong kernel: one block per CU; reduce blocks fill the CUs its last round leaves free
-    const int nred = reduce_slots(nconv, red, r, false);
+    const int nred = reduce_slots(nconv, c.red, r, false);
     if (mode == 6)
       conv_tap_pp_kernel<3><<<nconv + nred, 512, 0, stream>>>(RAG_PP_ARGS(nconv));
     else
@@ -984,29 +977,32 @@ bool rag_conv_tap_launch(const bf16* x, const bf16* w, const float* bias, bf16* 
   // fill the chip with 192-pixel ones: the ping-pong kernel with 48 x 96 wave tiles (MT = 3) -- two
   // waves per SIMD, where conv_tap_kernel below runs ONE 4-wave block per CU, one wave per SIMD,
   // with nothing to hide its LDS reads behind.
+  const int rows192 = max_slab_rows<kBM, 3>(c.S, c.WI, c.shift);
   const int n192 = ((M + kBM - 1) / kBM) * (COUTP / kBN);
-  if (n192 >= kPPMinBlocks && cached_rows <= kPPSlabRows192) {
-    const int nred = reduce_slots(n192, red, r, false);
+  if (n192 >= kPPMinBlocks && rows192 <= kPPSlabRows192) {
+    const int nred = reduce_slots(n192, c.red, r, false);
     conv_tap_pp_kernel<3, kNT, false, 3, 3><<<n192 + nred, 512, 0, stream>>>(RAG_PP_ARGS(n192));
     return true;
   }
 #undef RAG_PP_ARGS
-  if (cached_rows > kSlabRows) return false;
+  if (rows192 > kSlabRows) return false;
   // reduce blocks: the slots two-blocks-per-CU leave free on 256 CUs (30 at B = 256), at least 8
-  const int nc = ((M + kBM - 1) / kBM) * (COUTP / kBN);
   int nred = 0;
-  if (red) {
-    r = *red;
+  if (c.red) {
+    r = *c.red;
     r.ticket = nullptr;
-    nred = std::min(64, std::max(8, 2 * 256 - nc));
+    nred = std::min(64, std::max(8, 2 * 256 - n192));
   }
-  conv_tap_kernel<<<nc + nred, 256, 0, stream>>>(x, w, bias, y, mk, res, M, S, WI, shift, WO, HO,
-                                                 CIN, COUTP, YC, relu, HM, total_rows, nc, r);
+  conv_tap_kernel<<<n192 + nred, 256, 0, stream>>>(c.x, c.w, c.bias, c.y, c.mask, c.res, M, c.S,
+                                                   c.WI, c.shift, c.WO, c.HO, c.CIN, COUTP, c.YC,
+                                                   c.relu, c.HM, c.total_rows, n192, r);
   return true;
 }
 
 bool rag_conv_tap_bn_ok(int M, int S, int WI, int shift, int CIN, int COUTP, int KS) {
   const int nconv = ((M + kPPBM - 1) / kPPBM) * (COUTP / 128);
   return tap_mode() && KS == 3 && COUTP % kBN != 0 && COUTP % 128 == 0 && CIN % kBK == 0 &&
-         CIN >= kBK && nconv >= kPPMinBlocks && max_slab_rows(S, WI, shift, kPPBM) <= kPPSlabRows;
+         CIN >= kBK && nconv >= kPPMinBlocks &&
+         max_slab_rows<kPPBM, 3>(S, WI, shift) <= kPPSlabRows;
 }
+

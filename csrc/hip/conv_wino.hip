@@ -35,9 +35,12 @@
 //     the row-bit-2 swizzle keeps it conflict-free;
 //   * one barrier per chunk-phase (the V buffer flip); no per-step barriers, the two waves of
 //     a SIMD overlap freely.
+#include <atomic>
+
 #include "common.h"
+#include "conv_host.h"
 #include "pack.h"
-#include "wgrad_part.h"
+#include "rag_api.h"
 
 using namespace rag;
 
@@ -673,16 +676,18 @@ static bool wino_half_ok(int S, int NOUT) {
   const int TJ = (S + 1) / 2;
   return NOUT % 192 == 0 && wino_boards_per_block(S) == 1 && S * TJ > kHalfPairs;
 }
+// CUs of the device, kept once a device answered (no device visible: 0, and asked again).
 static int wino_cus() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0, n = 0;
+  static std::atomic<int> cus{0};
+  int n = cus.load(std::memory_order_relaxed);
+  if (!n) {
+    int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess ||
         hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
       return 0;
-    cus = n;
+    cus.store(n, std::memory_order_relaxed);
   }
-  return cus;
+  return n;
 }
 // 1: one-board blocks, 2: half-board blocks, 0: neither (the direct kernel).
 // A grid of at most one wave of blocks (one per CU) costs one block's time whatever its size, and
@@ -705,16 +710,14 @@ static int wino_mode(int B, int S, int KIN, int NOUT) {
   if (half && fills(2 * full)) return 2;
   return 0;
 }
-RAG_API int rag_conv_wino_prefer(int B, int S, int KIN, int NOUT) {
-  return wino_mode(B, S, KIN, NOUT) != 0;
-}
 RAG_API int rag_conv_wino_mode(int B, int S, int KIN, int NOUT) {
   return wino_mode(B, S, KIN, NOUT);
 }
 
 // Winograd 3x3 conv (forward or dgrad): X [B][S+2][S+2][KIN] bf16, U the layer's fragment-major
 // Winograd weights (rag_wino_pack), Y padded with halo HO and YC >= NOUT channels, mask (dgrad) with halo HM.
-// `pending`: a deferred wgrad reduction handle (conv.hip PendingRed) or null.
+// `red`: a pending wgrad reduction riding along the launch (taken from the caller's PendingRed
+// by rag_conv_wino in conv.hip) or null.
 // half (192-wide tiles only): run half-board blocks whenever the shape has them (wino_half_ok),
 // not only when the one-board grid would leave a ragged wave -- for launches that share the chip
 // with long resident kernels (the search's GPU rollouts hold a 128-VGPR wave on most CUs: a
@@ -779,13 +782,6 @@ int rag_conv_wino_bn_launch(const void* X, const void* W, const float* bias, voi
         (const bf16*)X, (const bf16*)W, bias, (bf16*)Y, (const bf16*)mask, B, S, KIN, NOUT, HO,
         YC, relu, HM, 1, r, WinoBN{mcoef, nullptr, spart, smean});
   return (int)hipGetLastError();
-}
-
-RAG_API int rag_conv_wino(const void* X, const void* W, const float* bias, void* Y,
-                          const void* mask, int B, int S, int KIN, int NOUT, int HO, int YC,
-                          int relu, int HM, hipStream_t stream) {
-  return rag_conv_wino_launch(X, W, bias, Y, mask, B, S, KIN, NOUT, HO, YC, relu, HM, stream,
-                              nullptr, 0);
 }
 
 // table: kWinoPackFields int64 per layer (W, COUT, CIN, COUTP, CINP, Uf or 0, Ub or 0, Wd or 0).

@@ -16,6 +16,7 @@
 //     ladder reading is a deep sequential search and stays in the native engine).
 // Output: uint8 [n][F][S*S] in the order of `fids`, the layout batch_features produces.
 #include "common.h"
+#include "rag_api.h"
 
 using namespace rag;
 

@@ -9,6 +9,7 @@
 // 2 = REINFORCE log_loss (Keras: -y log clip(p), averaged over the S*S classes and the batch;
 // reinforcement_policy_trainer.py:89-94), each sample scaled by an optional signed weight.
 #include "common.h"
+#include "rag_api.h"
 
 using namespace rag;
 
@@ -524,59 +525,36 @@ RAG_API int rag_pass_grads(const float* zout, const float* dpass, float* dW, flo
   return (int)hipGetLastError();
 }
 
+// Policy head forward. acc (optional, float[2]): += sum of the batch's losses, += number of
+// top-1 hits. dzsum (optional) [B]: each board's sum of dz (the head bias gradient's per-board
+// term, summed in a fixed order by rag_head_bwd).
+// With a pass logit (pass_w [S*S], pass_b [1]; both or neither): probs [B, S*S + 1], labels may
+// be S*S (pass), zout [B, S*S] receives the position logits and dpass [B] dL/d(pass logit) for
+// the PassLogit weight gradients (dW = dpass^T zout, db = sum dpass); dz already carries
+// dpass * pass_w. Without pass_w the kernel reads none of pass_b, zout, dpass.
 RAG_API int rag_policy_head_fwd(const void* H, const float* w, const float* b0,
-                                const float* pbias, float* probs, const int64_t* labels,
-                                const float* sweight, float* loss, float* dz, float* hit,
-                                float* acc, int B, int S, int KP, int K, int mode, float gscale,
-                                hipStream_t stream) {
-  // acc (optional, float[2]): += sum of the batch's losses, += number of top-1 hits
-  const size_t sm = (size_t)(((S * S + 4) & ~3) + KP) * sizeof(float);
-  policy_head_fwd_kernel<<<B, kHeadFwdThreads, sm, stream>>>((const bf16*)H, w, b0, pbias, probs,
-                                                          labels, sweight, loss, dz, hit, nullptr,
-                                                          nullptr, nullptr, nullptr, acc, S, KP,
-                                                          K, mode, gscale);
-  return (int)hipGetLastError();
-}
-
-// As rag_policy_head_fwd, plus dzsum [B]: each board's sum of dz (the head bias gradient's
-// per-board term, summed in a fixed order by rag_head_bwd_m).
-RAG_API int rag_policy_head_fwd_s(const void* H, const float* w, const float* b0,
-                                  const float* pbias, float* probs, const int64_t* labels,
-                                  const float* sweight, float* loss, float* dz, float* hit,
-                                  float* acc, float* dzsum, int B, int S, int KP, int K, int mode,
-                                  float gscale, hipStream_t stream) {
-  const size_t sm = (size_t)(((S * S + 4) & ~3) + KP) * sizeof(float);
-  policy_head_fwd_kernel<<<B, kHeadFwdThreads, sm, stream>>>((const bf16*)H, w, b0, pbias, probs,
-                                                          labels, sweight, loss, dz, hit, nullptr,
-                                                          nullptr, nullptr, nullptr, acc, S, KP,
-                                                          K, mode, gscale, dzsum);
-  return (int)hipGetLastError();
-}
-
-// With a pass logit (pass_w [S*S], pass_b [1]): probs [B, S*S + 1], labels may be S*S (pass),
-// zout [B, S*S] receives the position logits and dpass [B] dL/d(pass logit) for the PassLogit
-// weight gradients (dW = dpass^T zout, db = sum dpass); dz already carries dpass * pass_w.
-RAG_API int rag_policy_head_pass_fwd(const void* H, const float* w, const float* b0,
-                                     const float* pbias, const float* pass_w,
-                                     const float* pass_b, float* probs, const int64_t* labels,
-                                     const float* sweight, float* loss, float* dz, float* hit,
-                                     float* zout, float* dpass, float* acc, int B, int S, int KP,
-                                     int K, int mode, float gscale, hipStream_t stream) {
-  if (!pass_w || !pass_b) return -1;
+                                const float* pbias, const float* pass_w, const float* pass_b,
+                                float* probs, const int64_t* labels, const float* sweight,
+                                float* loss, float* dz, float* hit, float* zout, float* dpass,
+                                float* acc, float* dzsum, int B, int S, int KP, int K, int mode,
+                                float gscale, hipStream_t stream) {
+  if (pass_w && !pass_b) return -1;
   const size_t sm = (size_t)(((S * S + 4) & ~3) + KP) * sizeof(float);
   policy_head_fwd_kernel<<<B, kHeadFwdThreads, sm, stream>>>((const bf16*)H, w, b0, pbias, probs,
                                                           labels, sweight, loss, dz, hit, pass_w,
                                                           pass_b, zout, dpass, acc, S, KP, K,
-                                                          mode, gscale);
+                                                          mode, gscale, dzsum);
   return (int)hipGetLastError();
 }
 
 // mloss / mhit / acc (optional): the head forward's per-board loss and top-1 hit (written with
 // a null acc), summed into the running metrics acc[0..1] by one extra reduce block.
-RAG_API int rag_head_bwd_m(const void* H, const float* w, const float* dz, void* dH, float* dw,
-                           float* db0, float* dpbias, float* work, int B, int S, int KP, int K,
-                           int relu_mask, const float* mloss, const float* mhit, float* acc,
-                           const float* dzsum, hipStream_t stream) {
+// dzsum (optional): the head forward's per-board sums of dz; db0 is summed from them (or from dz
+// itself) in a fixed order.
+RAG_API int rag_head_bwd(const void* H, const float* w, const float* dz, void* dH, float* dw,
+                         float* db0, float* dpbias, float* work, int B, int S, int KP, int K,
+                         int relu_mask, const float* mloss, const float* mhit, float* acc,
+                         const float* dzsum, hipStream_t stream) {
   // work: >= rag_head_bwd_workspace(B, S, KP) floats
   const int npix = B * S * S;
   int nblk = (npix + 47) / 48;
@@ -597,13 +575,6 @@ RAG_API int rag_head_bwd_m(const void* H, const float* w, const float* dz, void*
   head_bwd_reduce_kernel<<<rblocks + 1, 1024, 0, stream>>>(
       work, dz, dw, db0, dpbias, nblk, B, S * S, KP, K, mloss, mhit, acc, dzsum);
   return (int)hipGetLastError();
-}
-
-RAG_API int rag_head_bwd(const void* H, const float* w, const float* dz, void* dH, float* dw,
-                         float* db0, float* dpbias, float* work, int B, int S, int KP, int K,
-                         int relu_mask, hipStream_t stream) {
-  return rag_head_bwd_m(H, w, dz, dH, dw, db0, dpbias, work, B, S, KP, K, relu_mask, nullptr,
-                        nullptr, nullptr, nullptr, stream);
 }
 
 RAG_API size_t rag_head_bwd_workspace(int B, int S, int KP) {

@@ -25,6 +25,7 @@
 // Positions that enforce positional superko keep the native search (host), since their
 // legality depends on the game history.
 #include "common.h"
+#include "rag_api.h"
 
 using namespace rag;
 

@@ -3,6 +3,7 @@
 // host; here   v = momentum * v - lr_t * (g + wd * p);  p += nesterov ? momentum * v - lr_t * g' : v
 // over one flat fp32 parameter buffer (all layers, a single launch), vectorised 4-wide.
 #include "common.h"
+#include "rag_api.h"
 
 namespace {
 

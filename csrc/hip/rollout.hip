@@ -28,6 +28,7 @@
 // of game after two passes with WHITE to move (Q3), area score with single-point eyeish
 // empties and komi, minus passes (Q12).
 #include "common.h"
+#include "rag_api.h"
 
 using namespace rag;
 

@@ -13,6 +13,7 @@
 //   the row has no candidate). Greedy ties resolve to the lowest index (python max() over the
 //   x-major legal-move list).
 #include "common.h"
+#include "rag_api.h"
 
 using namespace rag;
 

@@ -17,6 +17,7 @@
 // Loss (Keras 'mse' with sample weights, quirk-compatible with the generic executor):
 //   L = mean_b( (v_b - y_b)^2 * w_b ),  w_b = sw_b / mean_b(sw_b != 0)   (w_b = 1 without sw)
 #include "common.h"
+#include "rag_api.h"
 
 namespace rag {
 namespace {

@@ -18,6 +18,7 @@
 // this keeps every read bank-conflict free for ANY tap shift with no XOR swizzle, so all LDS
 // addresses are a per-lane base plus an immediate.
 #include "common.h"
+#include "conv_host.h"
 
 using namespace rag;
 

@@ -32,7 +32,8 @@
 #include <cstring>
 
 #include "common.h"
-#include "wgrad_part.h"
+#include "conv_host.h"
+#include "rag_api.h"
 
 using namespace rag;
 
@@ -456,7 +457,6 @@ wgrad_slab_reduce_kernel(WgradRed red) {
 // Applicability: 3x3, G and X both halo 1, 192 output channels, CINP == 192 (its six 32-channel
 // c-tiles also split the 192 bias columns), and the X slab covering every tap window of a stage
 // (64 + 2*WP + 2 <= 112). RAG_WGRAD_SLAB=0 disables it.
-bool rag_wgrad_slab_bf16();
 bool rag_wgrad_slab_ok(int S, int H, int HG, int GC, int COUTP, int CINP, int KS) {
   static const bool on = [] {
     const char* e = getenv("RAG_WGRAD_SLAB");

@@ -1,4 +1,5 @@
-"""ctypes signatures of the C ABI exported by rocalphago_amd/_hipkernels.so (csrc/hip/*.hip)."""
+"""ctypes signatures of the C ABI exported by rocalphago_amd/_hipkernels.so: one row per
+prototype in csrc/hip/rag_api.h (tests/test_native_symbols.py compares the two)."""
 import ctypes as C
 
 P = C.c_void_p
@@ -9,28 +10,22 @@ SZ = C.c_size_t
 
 SIGNATURES = {
     # conv.hip
-    "rag_conv_igemm": [P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, P, P],
-    "rag_conv_igemm_cin": [P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, P, P, I],
+    "rag_conv_igemm": [P] * 6 + [I] * 10 + [P, P, I, P, P, P, P],
     "rag_conv_wgrad_workspace": [I, I, I, I, I, P],
-    "rag_conv_wgrad": [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, P, P],
-    "rag_conv_wgrad_deferred": [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, P, P],
-    "rag_conv_igemm_bn": [P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, P, P, P, P, P, P],
+    "rag_conv_wgrad": [P] * 5 + [I] * 11 + [P, P, P],
     "rag_conv_bn_stat_blocks": [I, I, I],
     "rag_conv_bn_fusable": [I, I, I, I, I, I],
-    "rag_conv_wgrad_deferred_bn": [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, P, P, P],
     "rag_wgrad_flush": [P, P],
     "rag_wgrad_pending_bytes": [],
     "rag_wgrad_pending_init": [P],
     "rag_wgrad_pending_free": [P],
     "rag_pack_weights": [P, P, P, I, I, I, I, I, P],
     "rag_pack_trunk": [P, I, I, I64, P, I64, F, F, I],
-    # conv_wino.hip (+ the pending-handle entry in conv.hip)
+    # conv_wino.hip (+ the pending-handle entries in conv.hip)
     "rag_conv_wino_ok": [I, I, I, I, I],
-    "rag_conv_wino": [P, P, P, P, P, I, I, I, I, I, I, I, I, P],
-    "rag_conv_wino_p": [P, P, P, P, P, I, I, I, I, I, I, I, I, P, P, I],
+    "rag_conv_wino": [P] * 5 + [I] * 8 + [P, P, I],
     "rag_wino_pack": [P, I, I, P, I64, F, F, I],
     "rag_pack_step": [P, I, P, I, I, I, I, P, I64, F, F, I, P, I64, I64, I64, I64],
-    "rag_conv_wino_prefer": [I, I, I, I],
     "rag_conv_wino_mode": [I, I, I, I],
     "rag_conv_wino_bn_ok": [I, I, I, I],
     "rag_conv_wino_bn": [P] * 6 + [I] * 8 + [P] * 6,
@@ -40,12 +35,8 @@ SIGNATURES = {
     "rag_unpack": [P, P, I, I, I, I, I, P],
     "rag_pack_nchw": [P, P, I, I, I, I, I, P],
     # head.hip
-    "rag_policy_head_fwd": [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, F, P],
-    "rag_policy_head_pass_fwd": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, F,
-                                 P],
-    "rag_head_bwd": [P, P, P, P, P, P, P, P, I, I, I, I, I, P],
-    "rag_head_bwd_m": [P, P, P, P, P, P, P, P, I, I, I, I, I, P, P, P, P, P],
-    "rag_policy_head_fwd_s": [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, F, P],
+    "rag_policy_head_fwd": [P] * 16 + [I, I, I, I, I, F, P],
+    "rag_head_bwd": [P] * 8 + [I] * 5 + [P] * 5,
     "rag_head_bwd_workspace": [I, I, I],
     "rag_head_linear": [P, P, P, P, I, I, I, I, P],
     "rag_value_mlp_fwd": [P, P, P, P, P, P, P, P, I, I, I, I, P],
@@ -76,7 +67,7 @@ SIGNATURES = {
     # ladder.hip
     "rag_ladder_workspace": [I, I],
     "rag_ladders": [P, P, I, I, P, P, P],
-    "rag_conv_order": [I],
+    # conv_tap.hip, wgrad_slab.hip (A/B setters the tests drive)
     "rag_conv_tap_mode": [I],
     "rag_wgrad_slab_part_bf16": [I],
     "rag_wgrad_slab_map": [I],
@@ -90,8 +81,6 @@ RESTYPES = {"rag_conv_wgrad_workspace": SZ, "rag_head_bwd_workspace": SZ,
 
 def declare(lib):
     for name, args in SIGNATURES.items():
-        fn = getattr(lib, name, None)
-        if fn is None:
-            continue  # optional kernels added in later milestones
+        fn = getattr(lib, name)  # AttributeError: the library lacks a listed symbol
         fn.argtypes = args
         fn.restype = RESTYPES.get(name, I)

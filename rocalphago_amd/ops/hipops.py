@@ -152,16 +152,12 @@ def conv_igemm(x, wpack, bias, y, B, S, hi, ho, cinp, coutp, ks, relu, mask=None
         raise ValueError("mask layout does not match (halo %d, %d channels)" % (hm, y.shape[-1]))
     if residual is not None and residual.shape[1:] != y.shape[1:]:
         raise ValueError("residual layout does not match the output")
-    if cin is not None and cin < cinp:
-        # the real input channel count lets the 5x5 input layer skip its zero channels
-        _check(_lib().rag_conv_igemm_cin(_ptr(x), _ptr(wpack), _ptr(bias), _ptr(y), _ptr(mask),
-                                         _ptr(residual), B, S, hi, ho, cinp, coutp, y.shape[-1],
-                                         ks, int(relu), hm, _stream(), _hptr(pending), int(cin)),
-               "conv_igemm")
-        return y
+    # the real input channel count (0: all of cinp) lets the 5x5 input layer skip its zero channels
+    cin_real = int(cin) if cin is not None and cin < cinp else 0
     _check(_lib().rag_conv_igemm(_ptr(x), _ptr(wpack), _ptr(bias), _ptr(y), _ptr(mask),
                                  _ptr(residual), B, S, hi, ho, cinp, coutp, y.shape[-1], ks,
-                                 int(relu), hm, _stream(), _hptr(pending)), "conv_igemm")
+                                 int(relu), hm, _stream(), _hptr(pending), cin_real, None, None,
+                                 None, None), "conv_igemm")
     return y
 
 
@@ -174,7 +170,7 @@ def conv_wino_ok(S, hi, kin, nout, ks):
 def conv_wino_prefer(B, S, kin, nout):
     """True if conv_wino should take this layer at batch B rather than the direct kernel: one
     board per block and a last wave of blocks that fills at least 7/8 of the CUs."""
-    return bool(_lib().rag_conv_wino_prefer(B, S, kin, nout))
+    return conv_wino_mode(B, S, kin, nout) != 0
 
 
 def conv_wino_mode(B, S, kin, nout):
@@ -239,9 +235,9 @@ def conv_wino(x, u, bias, y, B, S, kin, nout, ho, relu, mask=None, mask_halo=Non
         raise ValueError("conv_wino input must have halo 1 and %d channels" % kin)
     if mask is not None and (mask.shape[1] != S + 2 * hm or mask.shape[-1] != y.shape[-1]):
         raise ValueError("mask layout does not match (halo %d, %d channels)" % (hm, y.shape[-1]))
-    _check(_lib().rag_conv_wino_p(_ptr(x), _ptr(u), _ptr(bias), _ptr(y), _ptr(mask), B, S, kin,
-                                  nout, ho, y.shape[-1], int(relu), hm, _stream(),
-                                  _hptr(pending), int(bool(half))), "conv_wino")
+    _check(_lib().rag_conv_wino(_ptr(x), _ptr(u), _ptr(bias), _ptr(y), _ptr(mask), B, S, kin,
+                                nout, ho, y.shape[-1], int(relu), hm, _stream(),
+                                _hptr(pending), int(bool(half))), "conv_wino")
     return y
 
 
@@ -303,11 +299,12 @@ def conv_igemm_bn(x, wpack, bias, y, B, S, cinp, coutp, relu, bn_coef=None, mask
         raise ValueError("mask layout does not match (halo 1, %d channels)" % y.shape[-1])
     if (mask is None) != (mask_coef is None):
         raise ValueError("mask and mask_coef go together")
-    _check(_lib().rag_conv_igemm_bn(_ptr(x), _ptr(wpack), _ptr(bias), _ptr(y), _ptr(mask),
-                                    _ptr(residual), B, S, 1, 1, cinp, coutp, y.shape[-1],
-                                    int(relu), 1, _stream(),
-                                    _hptr(pending), _ptr(bn_coef), _ptr(mask_coef),
-                                    _ptr(stat_part), _ptr(stat_mean)),
+    if bn_coef is None and mask_coef is None and stat_part is None:
+        _check(-5, "conv_igemm_bn")  # no fused form asked for (the plain one is conv_igemm)
+    _check(_lib().rag_conv_igemm(_ptr(x), _ptr(wpack), _ptr(bias), _ptr(y), _ptr(mask),
+                                 _ptr(residual), B, S, 1, 1, cinp, coutp, y.shape[-1], 3,
+                                 int(relu), 1, _stream(), _hptr(pending), 0, _ptr(bn_coef),
+                                 _ptr(mask_coef), _ptr(stat_part), _ptr(stat_mean)),
            "conv_igemm_bn")
     return y
 
@@ -410,11 +407,8 @@ def wgrad_workspace(B, S, coutp, cinp, ks, device):
 
 
 def conv_wgrad(g, x, dw, db, B, S, hi, cout, coutp, cin, cinp, ks, accumulate=False, work=None,
-               hg=None, reduce_stream=None, defer=False, pending=None, xcoef=None):
+               hg=None, defer=False, pending=None, xcoef=None):
     """dW (OIHW fp32) and db from dL/dpre g [pad hg] and the layer input x [pad hi].
-    ``reduce_stream`` (a torch stream): run the partial-slab reduction there, ordered after the
-    wgrad kernel by an event, so it overlaps the following kernels of the current stream; the
-    caller then owns the ordering of ``work`` reuse and of ``dw``/``db`` consumers.
     ``defer``: leave an fp16 partial-slab reduction pending in ``pending`` (a PendingReduction,
     required); the next ``conv_igemm(..., pending=pending)`` on this stream runs it in its free
     block slots (or ``wgrad_flush(pending)`` launches it). ``dw``/``db`` are final only after
@@ -425,27 +419,12 @@ def conv_wgrad(g, x, dw, db, B, S, hi, cout, coutp, cin, cinp, ks, accumulate=Fa
         work = wgrad_workspace(B, S, coutp, cinp, ks, g.device)
     if hg is None:
         hg = (g.shape[1] - S) // 2
-    if xcoef is not None:
-        if reduce_stream is not None:
-            raise ValueError("conv_wgrad(xcoef=...) has no reduce-stream form")
-        _check(_lib().rag_conv_wgrad_deferred_bn(_ptr(g), _ptr(x), _ptr(dw), _ptr(db), _ptr(work),
-                                                 B, S, hi, hg, g.shape[-1], cout, coutp, cin,
-                                                 cinp, ks, int(accumulate), _stream(),
-                                                 _hptr(pending) if defer else None, _ptr(xcoef)),
-               "conv_wgrad_bn")
-        return
-    if defer and reduce_stream is None:
-        if pending is None:
-            raise ValueError("conv_wgrad(defer=True) needs a PendingReduction handle")
-        _check(_lib().rag_conv_wgrad_deferred(_ptr(g), _ptr(x), _ptr(dw), _ptr(db), _ptr(work), B,
-                                              S, hi, hg, g.shape[-1], cout, coutp, cin, cinp, ks,
-                                              int(accumulate), _stream(), pending.ptr),
-               "conv_wgrad_deferred")
-        return
-    rs = ctypes.c_void_p(reduce_stream.cuda_stream) if reduce_stream is not None else None
+    if defer and pending is None and xcoef is None:
+        raise ValueError("conv_wgrad(defer=True) needs a PendingReduction handle")
     _check(_lib().rag_conv_wgrad(_ptr(g), _ptr(x), _ptr(dw), _ptr(db), _ptr(work), B, S, hi, hg,
                                  g.shape[-1], cout, coutp, cin, cinp, ks, int(accumulate),
-                                 _stream(), rs), "conv_wgrad")
+                                 _stream(), _hptr(pending) if defer else None, _ptr(xcoef)),
+           "conv_wgrad")
 
 
 def wgrad_flush(pending):
@@ -509,23 +488,13 @@ def policy_head_fwd(h, w, b0, pbias, probs, K, labels=None, sweight=None, loss=N
     S = WP - 2
     if acc is not None and (acc.dtype != torch.float32 or acc.numel() < 2):
         raise ValueError("acc must be an fp32 tensor of >= 2 elements")
-    if pass_w is not None:
-        _check(_lib().rag_policy_head_pass_fwd(
-            _ptr(h), _ptr(w), _ptr(b0), _ptr(pbias), _ptr(pass_w), _ptr(pass_b), _ptr(probs),
-            _ptr(labels), _ptr(sweight), _ptr(loss), _ptr(dz), _ptr(hit), _ptr(zout),
-            _ptr(dpass), _ptr(acc), B, S, KP, K, mode, float(gscale), _stream()),
-            "policy_head_pass_fwd")
-        return
-    if dzsum is not None:  # + each board's sum of dz (head_bwd's fixed-order db0)
-        _check(_lib().rag_policy_head_fwd_s(_ptr(h), _ptr(w), _ptr(b0), _ptr(pbias), _ptr(probs),
-                                            _ptr(labels), _ptr(sweight), _ptr(loss), _ptr(dz),
-                                            _ptr(hit), _ptr(acc), _ptr(dzsum), B, S, KP, K, mode,
-                                            float(gscale), _stream()), "policy_head_fwd")
-        return
-    _check(_lib().rag_policy_head_fwd(_ptr(h), _ptr(w), _ptr(b0), _ptr(pbias), _ptr(probs),
-                                      _ptr(labels), _ptr(sweight), _ptr(loss), _ptr(dz),
-                                      _ptr(hit), _ptr(acc), B, S, KP, K, mode, float(gscale),
-                                      _stream()), "policy_head_fwd")
+    if pass_w is not None and dzsum is not None:
+        raise ValueError("policy_head_fwd: dzsum has no pass-logit form")
+    # without pass_w the kernel touches none of pass_b / zout / dpass
+    _check(_lib().rag_policy_head_fwd(
+        _ptr(h), _ptr(w), _ptr(b0), _ptr(pbias), _ptr(pass_w), _ptr(pass_b), _ptr(probs),
+        _ptr(labels), _ptr(sweight), _ptr(loss), _ptr(dz), _ptr(hit), _ptr(zout), _ptr(dpass),
+        _ptr(acc), _ptr(dzsum), B, S, KP, K, mode, float(gscale), _stream()), "policy_head_fwd")
 
 
 def pass_grads(zout, dpass, dW, db):
@@ -561,9 +530,9 @@ def head_bwd(h, w, dz, dh, dw, db0, dpbias, K, relu_mask=True, work=None, metric
     if dzsum is not None and dzsum.numel() < B:
         raise ValueError("head_bwd dzsum: [B] per-board sums expected")
     # db0 in a fixed summation order (from dzsum, or from dz itself when the forward gave none)
-    _check(_lib().rag_head_bwd_m(_ptr(h), _ptr(w), _ptr(dz), _ptr(dh), _ptr(dw), _ptr(db0),
-                                 _ptr(dpbias), _ptr(work), B, S, KP, K, int(relu_mask),
-                                 _ptr(ml), _ptr(mh), _ptr(acc), _ptr(dzsum), _stream()),
+    _check(_lib().rag_head_bwd(_ptr(h), _ptr(w), _ptr(dz), _ptr(dh), _ptr(dw), _ptr(db0),
+                               _ptr(dpbias), _ptr(work), B, S, KP, K, int(relu_mask),
+                               _ptr(ml), _ptr(mh), _ptr(acc), _ptr(dzsum), _stream()),
            "head_bwd")
 
 

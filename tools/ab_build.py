@@ -5,8 +5,9 @@ from two gpurun calls do not compare).
     python tools/ab_build.py REV csrc/hip/conv_tap.hip [...]   -> rocalphago_amd/_hipkernels_ab.so
     RAG_HIP_SO=rocalphago_amd/_hipkernels_ab.so python bench.py ...
 
-Every other source is the working tree's; symbols missing from the old sources are optional in
-ops/_abi.py."""
+Every other source is the working tree's. The old sources must export the current C ABI
+(csrc/hip/rag_api.h, ops/_abi.py): a revision with other entry points is compared from a
+checkout of its own."""
 import glob
 import os
 import subprocess
