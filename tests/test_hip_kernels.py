@@ -196,6 +196,35 @@ def test_head_bwd_bias_gradient_sums_all_of_dz(ops, B):
     assert rel_err(dw, ref_dw) < 1e-2
 
 
+def sgd_two_steps_match_float64(ops, n, momentum, wd, nesterov):
+    """Two consecutive steps of the Keras-1 rule in optim.hip's header (the second one starts
+    from a non-zero v) against float64: v = momentum v - lr (g + wd p);
+    p += nesterov ? momentum v - lr (g + wd p) : v; without a velocity buffer p -= lr (g + wd p).
+    The float64 reference uses the fp32-rounded hyperparameters the kernel receives; the
+    tolerance is a few fp32 ulps of it."""
+    dev = torch.device("cuda")
+    gen = torch.Generator()
+    gen.manual_seed(n % 1000 + int(100 * momentum) + int(nesterov))
+    p = torch.randn(n, generator=gen).to(dev)
+    v = torch.zeros(n, device=dev) if momentum else None
+    lr, mom, wdf = (float(torch.tensor(h, dtype=torch.float32)) for h in (0.1, momentum, wd))
+    rp = p.double()
+    rv = torch.zeros(n, dtype=torch.float64, device=dev)
+    for step in range(2):
+        g = torch.randn(n, generator=gen).to(dev)
+        ops.sgd_(p, g, 0.1, momentum=momentum, v=v, wd=wd, nesterov=nesterov)
+        gk = g.double() + wdf * rp
+        if v is None:
+            rp = rp - lr * gk
+        else:
+            rv = mom * rv - lr * gk
+            rp = rp + (mom * rv - lr * gk if nesterov else rv)
+        case = (n, momentum, wd, nesterov, step)
+        assert torch.allclose(p.double(), rp, rtol=1e-6, atol=1e-7), case
+        if v is not None:
+            assert torch.allclose(v.double(), rv, rtol=1e-6, atol=1e-7), case
+
+
 def test_sgd(ops):
     dev = torch.device("cuda")
     p = torch.randn(1001, device=dev)
@@ -207,6 +236,13 @@ def test_sgd(ops):
     p2 = p.clone()
     ops.sgd_(p, g, 0.1, momentum=0.9, v=v)
     assert torch.allclose(p, p2 - 0.1 * g, atol=1e-6)
+    # plain (with and without weight decay), momentum, momentum + weight decay, nesterov + weight
+    # decay; the last length takes two trips of the grid-stride loop (2048 blocks of 256 float4
+    # lanes) and leaves a 3-element tail
+    for momentum, wd, nesterov in [(0.0, 0.0, False), (0.0, 0.03, False), (0.9, 0.0, False),
+                                   (0.9, 0.03, False), (0.9, 0.03, True)]:
+        for n in (1, 3, 4, 1001, 2048 * 256 * 4 * 2 + 3):
+            sgd_two_steps_match_float64(ops, n, momentum, wd, nesterov)
 
 
 def test_dgrad_mixed_halos(ops):
