@@ -62,6 +62,8 @@ RAG_API int rag_pack_step(const int64_t* wtable, int nwino, const int64_t* ttabl
 RAG_API int rag_conv_tap_mode(int mode);
 RAG_API int rag_wgrad_slab_map(int m);
 RAG_API int rag_wgrad_slab_part_bf16(int on);
+// the slab weight gradient's row chunking: chunks (blocks per c-tile), *spc 64-row stages each
+RAG_API int rag_wgrad_slab_chunks(int R, int CINP, int KS, int pair5, int* spc);
 
 // ---- head.hip, value_bwd.hip
 RAG_API int rag_pass_grads(const float* zout, const float* dpass, float* dW, float* db, int B,

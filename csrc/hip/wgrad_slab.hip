@@ -29,7 +29,21 @@
 // halves it. Each partial already sums 42 x 64 rows in fp32, so the rounding is one bf16 ulp per
 // partial on a gradient that bf16 autocast training would round to bf16 as a whole.
 // RAG_WGRAD_PART=fp32 keeps the fp32 part[chunk][tap][n][c] slabs + wgrad_reduce_kernel.
+//
+// Main loop (template parameter PIPE; docs/KERNELS.md "one barrier per 128 rows"):
+//   * PIPE 2 (default): a ring of FOUR 64-row slots (124 KB at 192 channels, one block per CU)
+//     used as two pairs. One barrier per pair (128 rows, four k-steps), in front of the pair's
+//     first fragment reads; the next pair's LDS-DMA is issued behind the first k-step's MFMAs
+//     into the slots that barrier freed. Two fragment register sets: the reads of k-step j + 1
+//     are issued before the MFMAs of k-step j and retired behind them. 166 VGPRs with map 1
+//     (cap: 168 at 12 waves), 116 for the 5x5 rows, 182 at 128 channels (8 waves); no scratch.
+//   * PIPE 1: the pair barrier with one fragment set (140 VGPRs): what map 0 runs at 192
+//     channels, whose two sets of 2 + 9 fragments spill; instantiated for it alone.
+//   * PIPE 0: one barrier per 64-row stage on a 3-stage ring, every k-step read -> wait -> MFMA:
+//     the loop of the BN-prologue instantiation, whose 4-stage fetch/store pipeline is tied to
+//     that barrier, and the A/B alternative of the others (RAG_WGRAD_PIPE=0).
 #include <cstring>
+#include <type_traits>
 
 #include "common.h"
 #include "conv_host.h"
@@ -65,6 +79,16 @@ struct WS {
 
 __device__ __forceinline__ int swz_x(int row) { return ((row >> 2) & 1) << 1; }
 __device__ __forceinline__ int krow(int g, int q) { return (g & 1) * 4 + q + (g >> 1) * 8; }
+
+// tr_frag at immediate byte offsets O0 / O1 from one address register
+template <int O0, int O1>
+__device__ __forceinline__ bf16x8 tr_frag_at(uint32_t addr) {
+  static_assert(O0 >= 0 && O1 >= 0 && O0 < 65536 && O1 < 65536, "16-bit DS offset");
+  bf16x4 lo, hi;
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(lo) : "v"(addr), "n"(O0));
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(hi) : "v"(addr), "n"(O1));
+  return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+}
 
 // vmcnt(N) with N = `young` stages of this wave's loads (PER glds each) left in flight
 template <int PER>
@@ -116,7 +140,7 @@ template <int kMAP, int N = kN, int KS = 3> struct WMap {
 // re-read from one XCD's L2; its X slab starts ky rows down (64 + 4 rows of the 112 staged).
 // Partials per block: 5 x N x 32 in the map-0 C layout ("c-tile" = c-tile * 5 + ky for the
 // reduction); the N bias columns are split over those 5 * ntc pseudo c-tiles. fp16 partials only.
-template <int kNBUF, bool kBF, int kMAP, int N = kN, bool BNX = false, int KS = 3>
+template <int kNBUF, bool kBF, int kMAP, int N = kN, bool BNX = false, int KS = 3, int PIPE = 0>
 __global__ void __launch_bounds__(64 * WS<N>::Waves)
 wgrad_slab_kernel(const bf16* __restrict__ G, const bf16* __restrict__ X,
                   float* __restrict__ part, float* __restrict__ bpart, int R, int WP, int GC,
@@ -130,6 +154,7 @@ wgrad_slab_kernel(const bf16* __restrict__ G, const bf16* __restrict__ X,
   constexpr int kWaves = L::Waves, kBlk = KS == 3 ? L::Blk : L::Blk / 9 * KS,
                 kThreads = 64 * kWaves;
   static_assert(!BNX || kNBUF == 4, "the BN prologue pipeline assumes a 4-stage ring");
+  static_assert(PIPE == 0 || (PIPE <= 2 && !BNX && kNBUF == 4), "the pair loop: two pairs of 64-row slots");
   // BNX: a [2][64] float table of the column coefficients follows the staging ring (one
   // __shared__ object: see above)
   __shared__ __attribute__((aligned(16))) bf16 lds[kNBUF * kStage + (BNX ? 256 : 0)];
@@ -156,10 +181,12 @@ wgrad_slab_kernel(const bf16* __restrict__ G, const bf16* __restrict__ X,
   const int ky = pblk ? 2 * (pct - 5) : pct - ctile * kGrp;  // the slab's kernel row
   const int c0 = ctile * kC;
   const int steps = (R + kRows - 1) / kRows;
-  const int sbeg = chunk * spc;
+  // (the pair loop branches on these: keep them scalar -- the division leaves them in VGPRs)
+  const int sbeg = PIPE ? __builtin_amdgcn_readfirstlane(chunk * spc) : chunk * spc;
   int nsteps = steps - sbeg;
   nsteps = nsteps < spc ? nsteps : spc;
   nsteps = nsteps > 0 ? nsteps : 0;
+  if constexpr (PIPE > 0) nsteps = __builtin_amdgcn_readfirstlane(nsteps);
   // X slab row 0 <-> stage row 0 shifted by tap (0, 0) (5x5: by tap (ky, 0))
   const int xshift = KS == 3 ? -(WP + 1) : (ky - 2) * WP - 2;
 
@@ -260,6 +287,175 @@ wgrad_slab_kernel(const bf16* __restrict__ G, const bf16* __restrict__ X,
   const int brow = tid >> 5;                 // rows brow, brow + kThreads / 32, ...
   float bsum = 0.f;
 
+  if constexpr (PIPE > 0) {
+  // The pair loop. A pair is two 64-row sub-stages (four k-steps) in two of the ring's four
+  // slots (sub-stage t in slot t & 3), with ONE barrier in front of it; the next pair is in
+  // flight in the other two slots.
+  //   PIPE 1: every k-step reads its fragments, waits, multiplies (as the stage loop does).
+  //   PIPE 2: two fragment register sets: k-step j+1's reads are issued before k-step j's MFMAs
+  //           and retired (lgkmcnt(0)) behind them, so only a pair's first reads sit behind the
+  //           barrier. 2 x (NA + NT) fragments: map 1 fits the 168 VGPRs of 12 waves, map 0
+  //           does not.
+  // Each accumulator still sums its k-steps in row order: dW and db are bit-identical to PIPE 0.
+  // An odd nsteps ends in a half pair (two k-steps): nothing is staged or read for the missing
+  // sub-stage (a clamped row index would count the next chunk's rows twice). No MFMA block sits
+  // in a branch of the loop body.
+  // Fragment addresses: one VGPR per fragment holds its byte address in the current pair's
+  // first slot; sub-stage, k-step and row half are immediate offsets of the read (< 64 KiB).
+  constexpr int kPairBytes = 2 * kStage * 2;
+  constexpr int kSets = PIPE == 2 ? 2 : 1;
+  uint32_t ga[NA], xa[NT];
+#pragma unroll
+  for (int a = 0; a < NA; ++a) ga[a] = lds_addr(lds + goff[a]);
+#pragma unroll
+  for (int i = 0; i < NT; ++i) xa[i] = lds_addr(lds + xoff[i]);
+  bf16x8 fa[kSets][NA], fb[kSets][NT];
+  // k-step KK of the pair's sub-stage H -> fragment set SET
+  auto rd = [&](auto SET, auto H, auto KK) {
+    constexpr int set = decltype(SET)::value;
+    constexpr int og = decltype(H)::value * kStage * 2 + decltype(KK)::value * 32 * N * 2;
+    constexpr int ox = decltype(H)::value * kStage * 2 + decltype(KK)::value * 32 * kC * 2;
+#pragma unroll
+    for (int a = 0; a < NA; ++a) fa[set][a] = tr_frag_at<og, og + 16 * N * 2>(ga[a]);
+#pragma unroll
+    for (int i = 0; i < NT; ++i) fb[set][i] = tr_frag_at<ox, ox + 16 * kC * 2>(xa[i]);
+  };
+  auto next_pair = [&](int p) {  // the fragment addresses move to the other pair of slots
+    const int d = (p & 1) ? -kPairBytes : kPairBytes;
+#pragma unroll
+    for (int a = 0; a < NA; ++a) ga[a] += d;
+#pragma unroll
+    for (int i = 0; i < NT; ++i) xa[i] += d;
+  };
+  auto mm = [&](auto SET) {
+    constexpr int set = decltype(SET)::value;
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int i = 0; i < NT; ++i)
+#pragma unroll
+      for (int a = 0; a < NA; ++a) acc[i][a] = mfma16(fa[set][a], fb[set][i], acc[i][a]);
+    __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  // The lane's staging and bias geometry is recomputed at each use from an opaque copy of the
+  // thread index (a dozen VALU ops per piece, once per pair): hoisted out of the loop it stays
+  // live across the MFMA blocks and spills.
+  auto opaque_tid = [&]() {
+    int t = tid;
+    asm volatile("" : "+v"(t));
+    return t;
+  };
+  auto stage_pair = [&](int pp) {
+    const int ln = opaque_tid() & 63;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int t = 2 * pp + h;
+      if (t >= nsteps) break;
+      const int r0 = (sbeg + t) * kRows;
+      bf16* lg = lds + (t & 3) * kStage;
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        const int slot = (2 * w + k) * 64 + ln;
+        const int row = slot / kGChunks;
+        const int pc = slot - row * kGChunks;
+        int r = r0 + row;
+        r = r < R ? r : R - 1;  // past the end: the last padded row is halo (zero)
+        glds16(G + (size_t)r * GC + (pc ^ L::swz_g(row)) * 8, lg + (2 * w + k) * 512);
+      }
+      if (xw) {
+        const int xr = w * 16 + (ln >> 2);
+        int r = r0 + xshift + xr;
+        r = r < 0 ? 0 : (r < R ? r : R - 1);  // only ever paired with zero (halo) G rows
+        glds16(X + (size_t)r * CIN + c0 + (((ln & 3) ^ swz_x(xr)) * 8), lg + kGElems + w * 512);
+      }
+    }
+  };
+  auto bias_rows = [&](int t) {  // must complete before sub-stage t's slot is handed back
+    if (!do_bias) return;
+    const int ot = opaque_tid();
+    const int bc = pct * 32 + (ot & 31);
+    if (bc < N) {
+      const bf16* lb = lds + (t & 3) * kStage;
+      for (int r = ot >> 5; r < kRows; r += kThreads / 32)
+        bsum += (float)lb[r * N + (((bc >> 3) ^ L::swz_g(r)) << 3) + (bc & 7)];
+    }
+  };
+  // every glds of this wave in flight belongs to the pair the wait is for, except in the
+  // prologue, where pair 1 (0, 1 or 2 sub-stages) stays in flight
+  auto pair_barrier = [&](int young) {
+    if (xw)
+      wait_young<3>(young);
+    else
+      wait_young<2>(young);
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+  };
+  using I0 = std::integral_constant<int, 0>;
+  using I1 = std::integral_constant<int, 1>;
+  stage_pair(0);
+  stage_pair(1);
+  if (nsteps > 0) pair_barrier(nsteps - 2 < 0 ? 0 : (nsteps - 2 < 2 ? nsteps - 2 : 2));
+  // The LDS-DMA of pair p + 1 goes behind the MFMAs of pair p's first k-step
+  // (profiles/dma_placement_r4.txt), into the slots that pair p's barrier freed; the prologue
+  // has staged pairs 0 and 1. stage_pair skips what lies past the chunk.
+  const int nfull = nsteps >> 1;
+  for (int p = 0; p < nfull; ++p) {
+    if (p > 0) {
+      pair_barrier(0);
+      next_pair(p - 1);
+    }
+    rd(I0{}, I0{}, I0{});
+    lds_reads_done();
+    if constexpr (PIPE == 1) {
+      mm(I0{});
+      if (p > 0) stage_pair(p + 1);
+      rd(I0{}, I0{}, I1{});
+      lds_reads_done();
+      mm(I0{});
+      rd(I0{}, I1{}, I0{});
+      lds_reads_done();
+      mm(I0{});
+      rd(I0{}, I1{}, I1{});
+      lds_reads_done();
+      mm(I0{});
+    } else {
+      rd(I1{}, I0{}, I1{});
+      mm(I0{});
+      if (p > 0) stage_pair(p + 1);
+      lds_reads_done();
+      rd(I0{}, I1{}, I0{});
+      mm(I1{});
+      lds_reads_done();
+      rd(I1{}, I1{}, I1{});
+      mm(I0{});
+      lds_reads_done();
+      mm(I1{});
+    }
+    bias_rows(2 * p);
+    bias_rows(2 * p + 1);
+  }
+  if (nsteps & 1) {  // half pair
+    if (nfull > 0) {
+      pair_barrier(0);
+      next_pair(nfull - 1);
+    }
+    rd(I0{}, I0{}, I0{});
+    lds_reads_done();
+    if constexpr (PIPE == 1) {
+      mm(I0{});
+      rd(I0{}, I0{}, I1{});
+      lds_reads_done();
+      mm(I0{});
+    } else {
+      rd(I1{}, I0{}, I1{});
+      mm(I0{});
+      lds_reads_done();
+      mm(I1{});
+    }
+    bias_rows(nsteps - 1);
+  }
+  } else {
 #pragma unroll
   for (int k = 0; k < kNBUF - 1; ++k)
     if (k < nsteps) stage(k, k);
@@ -330,6 +526,7 @@ wgrad_slab_kernel(const bf16* __restrict__ G, const bf16* __restrict__ X,
         bsum += (float)lb[r * N + (((bcol >> 3) ^ L::swz_g(r)) << 3) + (bcol & 7)];
     }
   }
+  }  // PIPE == 0
 
   if (idle) {  // nothing to report (the reduction skips these slots)
 #pragma unroll
@@ -482,6 +679,10 @@ int rag_wgrad_slab_nchunks(int R, int CINP, int* spc, int KS, int pair5) {
   return (steps + s - 1) / s;
 }
 
+RAG_API int rag_wgrad_slab_chunks(int R, int CINP, int KS, int pair5, int* spc) {
+  return rag_wgrad_slab_nchunks(R, CINP, spc, KS, pair5);
+}
+
 static int g_wslab_bf = -1;    // block-scaled fp16 partial slabs unless RAG_WGRAD_PART=fp32
 static int g_wslab_map = -1;   // wave -> tile map (WMap), RAG_WGRAD_MAP
 
@@ -497,6 +698,18 @@ RAG_API int rag_wgrad_slab_map(int m) {
   const int old = g_wslab_map;
   g_wslab_map = m;
   return old;
+}
+
+// main loop of the kernels without BN prologue: the pair loop unless RAG_WGRAD_PIPE=0 (one
+// barrier per 64-row stage)
+static int g_wslab_pipe = -1;
+
+static int wslab_pipe() {
+  if (g_wslab_pipe < 0) {
+    const char* e = getenv("RAG_WGRAD_PIPE");
+    g_wslab_pipe = !(e && e[0] == '0');
+  }
+  return g_wslab_pipe;
 }
 
 RAG_API int rag_wgrad_slab_part_bf16(int on) {
@@ -550,57 +763,67 @@ int rag_launch_wgrad_slab_reduce(const WgradRed& r, hipStream_t stream) {
   return (int)hipGetLastError();
 }
 
+// One non-BNX instantiation family: the stage loop on a 3-slot ring or a pair loop on 4 slots.
+template <bool BF, int MP, int N, int KS>
+static void wslab_launch(int pipe, dim3 grid, hipStream_t stream, const bf16* G, const bf16* X,
+                         float* part, float* bpart, int R, int WP, int GC, int CIN, int spc,
+                         int CINP, int pair5, unsigned* ticket_reset) {
+#define RAG_WSLAB(NB, P)                                                                        \
+  wgrad_slab_kernel<NB, BF, MP, N, false, KS, P><<<grid, 64 * WS<N>::Waves, 0, stream>>>(       \
+      G, X, part, bpart, R, WP, GC, CIN, spc, CINP, nullptr, 0, pair5, kWslabPrio, ticket_reset)
+  if (!pipe) {
+    RAG_WSLAB(3, 0);
+  } else if constexpr (MP == 0 && N == kN && KS == 3) {
+    RAG_WSLAB(4, 1);  // two sets of 2 + 9 fragments spill at 168 VGPRs
+  } else {
+    RAG_WSLAB(4, 2);
+  }
+#undef RAG_WSLAB
+}
+
 int rag_launch_wgrad_slab(const bf16* G, const bf16* X, float* part, float* bpart, int R, int WP,
                           int GC, int CIN, int spc, int CINP, int nchunks, hipStream_t stream,
                           const float* xcoef, int S, int KS, int COUTP, int pair5,
                           unsigned* ticket_reset) {
   const bool bf = rag_wgrad_slab_bf16();
+  const int pipe = wslab_pipe();
   if (!bf) ticket_reset = nullptr;  // fp32 partials are never deferred
+#define RAG_WSLAB_ARGS G, X, part, bpart, R, WP, GC, CIN, spc, CINP
   if (KS == 5) {  // per-row blocks, fp16 partials, map 0
     if (!bf || xcoef) return -5;
     if (pair5 && CINP != 2 * kC) return -5;
     const dim3 g5(nchunks * (pair5 ? 8 : (CINP / kC) * 5));
     if (COUTP == 192)
-      wgrad_slab_kernel<3, true, 0, 192, false, 5><<<g5, 768, 0, stream>>>(
-          G, X, part, bpart, R, WP, GC, CIN, spc, CINP, nullptr, 0, pair5, kWslabPrio,
-          ticket_reset);
+      wslab_launch<true, 0, 192, 5>(pipe, g5, stream, RAG_WSLAB_ARGS, pair5, ticket_reset);
     else if (COUTP == 128)
-      wgrad_slab_kernel<3, true, 0, 128, false, 5><<<g5, 512, 0, stream>>>(
-          G, X, part, bpart, R, WP, GC, CIN, spc, CINP, nullptr, 0, pair5, kWslabPrio,
-          ticket_reset);
+      wslab_launch<true, 0, 128, 5>(pipe, g5, stream, RAG_WSLAB_ARGS, pair5, ticket_reset);
     else
       return -5;
     return (int)hipGetLastError();
   }
   const dim3 grid(nchunks * (CINP / kC));
-  if (xcoef) {  // BN prologue: 128 channels, fp16 partials
+  if (xcoef) {  // BN prologue: 128 channels, fp16 partials; its own 4-stage loop
     if (CINP != 128 || !bf || S > 64) return -5;
-    wgrad_slab_kernel<4, true, 0, 128, true><<<grid, 512, 0, stream>>>(G, X, part, bpart, R, WP,
-                                                                       GC, CIN, spc, CINP, xcoef,
-                                                                       S, 0, kWslabPrio,
-                                                                       ticket_reset);
+    wgrad_slab_kernel<4, true, 0, 128, true><<<grid, 512, 0, stream>>>(RAG_WSLAB_ARGS, xcoef, S, 0,
+                                                                       kWslabPrio, ticket_reset);
     return (int)hipGetLastError();
   }
-  if (CINP == 128) {  // 8 waves, map 0
-    if (bf)
-      wgrad_slab_kernel<3, true, 0, 128><<<grid, 512, 0, stream>>>(G, X, part, bpart, R, WP, GC,
-                                                                   CIN, spc, CINP, nullptr, 0, 0,
-                                                                   kWslabPrio, ticket_reset);
-    else
-      wgrad_slab_kernel<3, false, 0, 128><<<grid, 512, 0, stream>>>(G, X, part, bpart, R, WP, GC,
-                                                                    CIN, spc, CINP);
-    return (int)hipGetLastError();
-  }
-  // 192 channels: a 3-stage ring (4 / 5 measured no faster, deleted round 5); A/B axes: the
-  // fp32 partial slabs (RAG_WGRAD_PART=fp32) and the wave -> tile map (RAG_WGRAD_MAP=0)
-#define RAG_WSLAB(BF, MP)                                                                       \
-  wgrad_slab_kernel<3, BF, MP><<<grid, 64 * WS<kN>::Waves, 0, stream>>>(                       \
-      G, X, part, bpart, R, WP, GC, CIN, spc, CINP, nullptr, 0, 0, kWslabPrio, ticket_reset)
+  // A/B axes: the fp32 partial slabs (RAG_WGRAD_PART=fp32), at 192 channels the wave -> tile map
+  // (RAG_WGRAD_MAP=0), and the main loop (RAG_WGRAD_PIPE=0: one barrier per 64-row stage on a
+  // 3-stage ring; 4 / 5 stages measured no faster, deleted round 5)
   const int mp = wslab_map();
-  if (bf && mp) RAG_WSLAB(true, 1);
-  else if (bf) RAG_WSLAB(true, 0);
-  else if (mp) RAG_WSLAB(false, 1);
-  else RAG_WSLAB(false, 0);
-#undef RAG_WSLAB
+  if (CINP == 128) {  // 8 waves, map 0
+    if (bf) wslab_launch<true, 0, 128, 3>(pipe, grid, stream, RAG_WSLAB_ARGS, 0, ticket_reset);
+    else wslab_launch<false, 0, 128, 3>(pipe, grid, stream, RAG_WSLAB_ARGS, 0, ticket_reset);
+  } else if (bf && mp) {
+    wslab_launch<true, 1, kN, 3>(pipe, grid, stream, RAG_WSLAB_ARGS, 0, ticket_reset);
+  } else if (bf) {
+    wslab_launch<true, 0, kN, 3>(pipe, grid, stream, RAG_WSLAB_ARGS, 0, ticket_reset);
+  } else if (mp) {
+    wslab_launch<false, 1, kN, 3>(pipe, grid, stream, RAG_WSLAB_ARGS, 0, ticket_reset);
+  } else {
+    wslab_launch<false, 0, kN, 3>(pipe, grid, stream, RAG_WSLAB_ARGS, 0, ticket_reset);
+  }
+#undef RAG_WSLAB_ARGS
   return (int)hipGetLastError();
 }

@@ -71,6 +71,7 @@ SIGNATURES = {
     "rag_conv_tap_mode": [I],
     "rag_wgrad_slab_part_bf16": [I],
     "rag_wgrad_slab_map": [I],
+    "rag_wgrad_slab_chunks": [I, I, I, I, P],
 }
 
 RESTYPES = {"rag_conv_wgrad_workspace": SZ, "rag_head_bwd_workspace": SZ,
