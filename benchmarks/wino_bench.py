@@ -6,7 +6,12 @@
 
 Prints one JSON line: median / min microseconds per launch of every (kernel, pass), the
 effective dense-equivalent TFLOP/s (2 * B * 361 * 192 * 1728 FLOP per launch, i.e. what the
-direct algorithm would need) and the max relative difference of the two kernels' outputs."""
+direct algorithm would need) and the max relative difference of the two kernels' outputs.
+
+fwd_launch11 / fwd_chain11: a trunk's 11 forward layers (each its own weights, the same 12
+activation buffers) as 11 conv_wino launches and as one conv_wino_chain launch; microseconds per
+11 layers, and ``chain_boundary_us`` = their difference per removed launch boundary (median).
+Meaningful at batches that run one-board blocks (conv_wino_mode 1, e.g. 256)."""
 import argparse
 import json
 import os
@@ -53,13 +58,22 @@ def run(a, B):
         [ub] + [ub.clone() for _ in range(a.wcopies - 1)]
     bias = torch.randn(C, device=dev) * 0.1
     y = {k: ops.alloc_padded(B, S, 1, C, dev) for k in ("fd", "fw", "fh", "dd", "dw")}
+    NL = 11
+    acts = [ops.alloc_padded(B, S, 1, C, dev) for _ in range(NL)]
     it = {}
 
     def nxt(v):
         i = it[id(v)] = it.get(id(v), -1) + 1
         return v[i % len(v)]
 
+    def trunk():
+        bufs = [nxt(xps)] + acts
+        return [(bufs[l], nxt(ufs), bias, bufs[l + 1], True) for l in range(NL)]
+
     cases = {
+        "fwd_launch11": lambda: [ops.conv_wino(x_, u_, b_, y_, B, S, C, C, 1, r_)
+                                 for x_, u_, b_, y_, r_ in trunk()],
+        "fwd_chain11": lambda: ops.conv_wino_chain(trunk(), B, S, any_batch=True),
         "fwd_direct": lambda: ops.conv_igemm(nxt(xps), nxt(wfs), bias, y["fd"], B, S, 1, 1, C,
                                              C, 3, True),
         "fwd_wino": lambda: ops.conv_wino(nxt(xps), nxt(ufs), bias, y["fw"], B, S, C, C, 1,
@@ -89,8 +103,11 @@ def run(a, B):
     out = {"batch": B, "size": S}
     for k, ts in times.items():
         med = statistics.median(ts)
+        n = NL if k.endswith("11") else 1
         out[k] = {"median_us": round(med, 2), "min_us": round(min(ts), 2),
-                  "dense_equiv_tflops": round(flop / med / 1e6, 1)}
+                  "dense_equiv_tflops": round(n * flop / med / 1e6, 1)}
+    out["chain_boundary_us"] = round((out["fwd_launch11"]["median_us"] -
+                                      out["fwd_chain11"]["median_us"]) / (NL - 1), 2)
 
     def rel(p, q):
         p, q = ops.unpack(p, C, 1), ops.unpack(q, C, 1)

@@ -149,79 +149,98 @@ struct WinoBN {
 // Block (x, y): boards [x * nb, x * nb + nb), output channels [192 y, 192 y + 192).
 // SINGLE: one board per block (19x19): the V row of output pair m is m itself (pad pairs 190,
 // 191 read rows < 224 whose outputs are dropped), so no per-fragment row table is kept.
-template <int WN, bool SINGLE, int PAIRS = kWP, int BNM = 0>
-__global__ void __launch_bounds__(512, 1)
-conv_wino_kernel(const bf16* __restrict__ X, const bf16* __restrict__ U,
-                 const float* __restrict__ bias, bf16* __restrict__ Y,
-                 const bf16* __restrict__ mask, int B, int S, int KIN, int NOUT, int HO, int YC,
-                 int relu, int HM, int nb, WgradRed red, WinoBN bn = WinoBN{}) {
+//
+// The kernel is two pieces, so that one launch can run one layer (conv_wino_kernel) or a chain
+// of them (conv_wino_chain_kernel): the thread geometry of a block, the same for every layer it
+// runs (wino_geom), and the layer itself (wino_layer).
+template <bool SINGLE, int MT> struct WinoGeom {
+  int lane, wm, wn, frow, fq;
+  int TJ, PB, RPB;  // pair columns, output pairs and raw rows per board
+  int b0, n0, p0;   // first board, first output channel, first output pair (HALF) of the block
+  long total_rows;
+  int vb[SINGLE ? 1 : MT];  // V rows of this lane's output pairs (tap ky adds ky * TJ)
+  uint32_t uoff;            // byte offset of this lane's 8 elements in its wave's first fragment
+  int tu0, tu1;             // transform units of this thread (packed, see wino_geom)
+};
+
+// global loads are buffer loads: a wave-uniform descriptor (SGPRs), a 32-bit lane offset
+// and a uniform SGPR offset, one VGPR per address instead of 64-bit pointers (the kernel sat
+// at 256 VGPRs and its scratch reloads, being VMEM, forced vmcnt(0) waits on every weight
+// load in flight); the descriptor's range check also replaces the raw rows' clamp.
+__device__ __forceinline__ auto wino_rsrc(const void* p, long bytes) {
+  const uint64_t a = reinterpret_cast<uint64_t>(p);
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a);
+  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
+  const int nb = __builtin_amdgcn_readfirstlane((int)(bytes < 0x7fffffffL ? bytes : 0x7fffffffL));
+  return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)hi << 32) | lo),
+                                           (short)0, nb, 0x00020000);
+}
+
+// This XCD's L2 warmed with a layer's weights U (block x runs on XCD x % 8: its blocks each
+// touch one slice; in the step every launch finds its weights cold, and the in-loop weight
+// loads, one MFMA block ahead, then waited on HBM). Returns the XOR of the loaded words, which
+// the caller keeps alive (asm volatile) where it can afford the wait.
+template <typename R>
+__device__ __forceinline__ uint32_t wino_warm(const R& urs, int NOUT, int KIN) {
+  uint32_t warm = 0;
+  const int lin = blockIdx.y * gridDim.x + blockIdx.x;
+  const int per_xcd = (gridDim.x * gridDim.y + 7) >> 3;
+  const uint32_t slice = (uint32_t)((12L * NOUT * KIN * 2 + per_xcd - 1) / per_xcd);
+  const uint32_t base = (uint32_t)((lin >> 3) % per_xcd) * slice;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const uint32_t off = (uint32_t)(threadIdx.x + k * 512) * 16u;
+    const uint32_t o = off < slice ? base + off : 0xfffffff0u;  // out of range: reads 0
+    warm ^= (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(urs, o, 0, 0);
+  }
+  return warm;
+}
+
+template <int WN, bool SINGLE, int PAIRS>
+__device__ __forceinline__ WinoGeom<SINGLE, WinoTile<WN, PAIRS>::MT> wino_geom(int B, int S,
+                                                                              int nb) {
   using T = WinoTile<WN, PAIRS>;
-  constexpr int kWMT = T::MT, kWNT = T::NT, kWN = WN, kEpRow = T::EpRow;
+  constexpr int kWMT = T::MT;
   constexpr bool HALF = PAIRS == kHalfPairs;  // two blocks per board (SINGLE geometry)
   static_assert(!HALF || SINGLE, "half-board blocks: one board");
-  static_assert(BNM == 0 || (SINGLE && !HALF && WN == 128), "fused BN: the 128-wide one-board tile");
-  // + a [2][64] float column-statistics accumulator past the loop ring / epilogue image
-  __shared__ __attribute__((aligned(16))) bf16 lds[T::Lds + (BNM ? 256 : 0)];
-  float* sred = reinterpret_cast<float*>(lds + T::Lds);
-  if constexpr (BNM != 0) {
-    if (bn.spart && threadIdx.x < 128) sred[threadIdx.x] = 0.f;  // published by the first barrier
-  }
+  WinoGeom<SINGLE, kWMT> g;
   const int lane = lane_id();
   const int w = wave_id();
-  const int wm = w % T::MW, wn = w / T::MW;
-  const int frow = lane & 15, fq = lane >> 4;
+  g.lane = lane;
+  g.wm = w % T::MW;
+  g.wn = w / T::MW;
+  g.frow = lane & 15;
+  g.fq = lane >> 4;
   const int WI = S + 2, TJ = (S + 1) >> 1;
   const int PB = S * TJ;    // output pairs per board
   const int VPB = WI * TJ;  // V rows per board
   const int RPB = WI * WI;  // raw rows per board
-  const int b0 = HALF ? (int)(blockIdx.x >> 1) : (int)blockIdx.x * nb;
-  const int n0 = blockIdx.y * kWN;
+  g.TJ = TJ;
+  g.PB = PB;
+  g.RPB = RPB;
+  g.b0 = HALF ? (int)(blockIdx.x >> 1) : (int)blockIdx.x * nb;
+  g.n0 = blockIdx.y * WN;
   // HALF: this block's output pairs are [p0, p0 + 96) of the board; its V rows start at padded
   // row i0 (V row of pair p at ky: p - i0 TJ + ky TJ)
   const int p0 = HALF ? (int)(blockIdx.x & 1) * kHalfPairs : 0;
   const int i0 = HALF ? p0 / TJ : 0;
   const int voff = p0 - i0 * TJ;
-  const long total_rows = (long)B * RPB;
-  const int cchunks = KIN / kWK;
-  const int NK = 2 * cchunks;  // chunk-phases
-
-  // ---- V rows of this lane's output pairs (tap ky adds ky * TJ)
-  int vb[SINGLE ? 1 : kWMT];
+  g.p0 = p0;
+  g.total_rows = (long)B * RPB;
 #pragma unroll
   for (int i = 0; i < (SINGLE ? 1 : kWMT); ++i) {
-    int m = wm * (16 * kWMT) + i * 16 + frow;
+    int m = g.wm * (16 * kWMT) + i * 16 + g.frow;
     if (SINGLE) {
-      vb[i] = m + voff;
+      g.vb[i] = m + voff;
       continue;
     }
     m = m < nb * PB ? m : nb * PB - 1;  // pad pairs read a valid row, their output is dropped
     const int bl = m / PB, rem = m - bl * PB;
     const int ii = rem / TJ, t = rem - ii * TJ;
-    vb[i] = (bl * WI + ii) * TJ + t;
+    g.vb[i] = (bl * WI + ii) * TJ + t;
   }
-
-  // ---- global loads are buffer loads: a wave-uniform descriptor (SGPRs), a 32-bit lane offset
-  // and a uniform SGPR offset, one VGPR per address instead of 64-bit pointers (the kernel sat
-  // at 256 VGPRs and its scratch reloads, being VMEM, forced vmcnt(0) waits on every weight
-  // load in flight); the descriptor's range check also replaces the raw rows' clamp.
-  auto rsrc = [](const void* p, long bytes) {
-    const uint64_t a = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-    const int nb = __builtin_amdgcn_readfirstlane((int)(bytes < 0x7fffffffL ? bytes : 0x7fffffffL));
-    return __builtin_amdgcn_make_buffer_rsrc(
-        reinterpret_cast<void*>(((uint64_t)hi << 32) | lo), (short)0, nb, 0x00020000);
-  };
   // weight fragments: fragment (tap, chunk, nf) is 512 contiguous bf16, lane l's 8 at 8 l
-  const int NF = NOUT / 16;
-  const auto urs = rsrc(U, 12L * NOUT * KIN * 2);
-  const uint32_t uoff = (uint32_t)((((n0 >> 4) + wn * kWNT) * 512 + lane * 8) * 2);
-  auto wfrag = [&](int tap, int c, int j) {
-    const int so = ((tap * cchunks + c) * NF + j) * 1024;
-    return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(urs, uoff, so, 0));
-  };
-  // taps: set A q = 1 (phase 1) / 0 (phase 2), set B q = 2 / 3; tap (ky, q) = 4 ky + q
-
+  g.uoff = (uint32_t)((((g.n0 >> 4) + g.wn * T::NT) * 512 + lane * 8) * 2);
   // ---- transform units of this thread (the same for every chunk-phase): V row, 8-channel
   // group, raw row of d0 (named scalars: a runtime-indexed array went to scratch)
   // packed: V row (bits 0-9), 8-channel group (10-11), raw row of d0 (12-30), -1 = no unit
@@ -235,7 +254,50 @@ conv_wino_kernel(const bf16* __restrict__ X, const bf16* __restrict__ U,
     const int rr = (bl * WI + r + i0) * WI + 2 * t;
     return u < NU ? (v | ((u & 3) << 10) | (rr << 12)) : -1;
   };
-  const int tu0 = unit(0), tu1 = unit(1);
+  g.tu0 = unit(0);
+  g.tu1 = unit(1);
+  return g;
+}
+
+// One layer of a block: V transform, the two GEMM phases, epilogue. `lds`: T::Lds bf16 (+ the
+// BN forms' [2][64] float column accumulator past them).
+// CHAIN (conv_wino_chain_kernel): no prologue warming of its own weights (the previous layer
+// did it); instead the L2-warming loads of `Unext` (the next layer's weights, or any valid
+// weights after the last layer) go out before the epilogue, whose LDS image and stores hide them.
+// `urs`: the buffer descriptor of the layer's weights U (wino_rsrc over 12 NOUT KIN bf16), built
+// by the caller: conv_wino_kernel builds it BEFORE wino_geom, the order the kernel had before it
+// was split. With the descriptor built after the transform units the 192-wide one-board
+// instantiation went from 244 VGPRs to 256 and 20 bytes of scratch, nothing else changed.
+template <int WN, bool SINGLE, int PAIRS, int BNM, bool CHAIN, typename R>
+__device__ __forceinline__ void wino_layer(
+    const R& urs, bf16* lds, const WinoGeom<SINGLE, WinoTile<WN, PAIRS>::MT>& g,
+    const bf16* __restrict__ X, const float* __restrict__ bias, bf16* __restrict__ Y,
+    const bf16* __restrict__ mask, int B, int S, int KIN, int NOUT, int HO, int YC, int relu,
+    int HM, int nb, const WinoBN& bn, const bf16* Unext) {
+  using T = WinoTile<WN, PAIRS>;
+  constexpr int kWMT = T::MT, kWNT = T::NT, kWN = WN, kEpRow = T::EpRow;
+  constexpr bool HALF = PAIRS == kHalfPairs;
+  static_assert(BNM == 0 || (SINGLE && !HALF && WN == 128), "fused BN: the 128-wide one-board tile");
+  static_assert(!CHAIN || (BNM == 0 && !HALF), "chain: plain one- or multi-board blocks");
+  float* sred = reinterpret_cast<float*>(lds + T::Lds);
+  const int lane = g.lane, wm = g.wm, wn = g.wn, frow = g.frow, fq = g.fq;
+  const int TJ = g.TJ, PB = g.PB, RPB = g.RPB, b0 = g.b0, n0 = g.n0, p0 = g.p0;
+  const long total_rows = g.total_rows;
+  const int tu0 = g.tu0, tu1 = g.tu1;
+  const int cchunks = KIN / kWK;
+  const int NK = 2 * cchunks;  // chunk-phases
+  int vb[SINGLE ? 1 : kWMT];
+#pragma unroll
+  for (int i = 0; i < (SINGLE ? 1 : kWMT); ++i) vb[i] = g.vb[i];
+
+  const int NF = NOUT / 16;
+  const uint32_t uoff = g.uoff;
+  auto wfrag = [&](int tap, int c, int j) {
+    const int so = ((tap * cchunks + c) * NF + j) * 1024;
+    return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(urs, uoff, so, 0));
+  };
+  // taps: set A q = 1 (phase 1) / 0 (phase 2), set B q = 2 / 3; tap (ky, q) = 4 ky + q
+
   // BNM 1: per transform unit, the BN coefficients of its four raw columns d0..d3 (zero on halo
   // pixels and for a missing unit, so U = 0 there)
   float bcx[2][4], bcc[2][4];
@@ -256,7 +318,7 @@ conv_wino_kernel(const bf16* __restrict__ X, const bf16* __restrict__ U,
     }
   }
   // raw rows of this block's boards (out of range, i.e. the last block's +1 row, reads 0)
-  const auto xrs = rsrc(X + (long)b0 * RPB * KIN, (total_rows - (long)b0 * RPB) * KIN * 2);
+  const auto xrs = wino_rsrc(X + (long)b0 * RPB * KIN, (total_rows - (long)b0 * RPB) * KIN * 2);
   // The transform of V(kk) runs as four "ops" per thread and chunk-phase, two raw-pixel loads
   // each: op 2u + h of unit u (h = set): phase 1 loads (d1, d2) for both sets (V1 = d1 + d2,
   // V2 = d2 - d1), phase 2 (d0, d2) for set A (V0 = d0 - d2) and (d3, d1) for set B
@@ -354,22 +416,10 @@ conv_wino_kernel(const bf16* __restrict__ X, const bf16* __restrict__ U,
     }
   };
 
-  // ---- prologue: this XCD's L2 warmed with the layer's weights (block x runs on XCD x % 8:
-  // its blocks each touch one slice; in the step every launch finds its weights cold, and the
-  // in-loop weight loads, one MFMA block ahead, then waited on HBM), step (0, 0)'s weights, V(0)
+  // ---- prologue: this XCD's L2 warmed with the layer's weights (wino_warm; a chain did it
+  // during the previous layer), step (0, 0)'s weights, V(0)
   uint32_t warm = 0;
-  {
-    const int lin = blockIdx.y * gridDim.x + blockIdx.x;
-    const int per_xcd = (gridDim.x * gridDim.y + 7) >> 3;
-    const uint32_t slice = (uint32_t)((12L * NOUT * KIN * 2 + per_xcd - 1) / per_xcd);
-    const uint32_t base = (uint32_t)((lin >> 3) % per_xcd) * slice;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const uint32_t off = (uint32_t)(threadIdx.x + k * 512) * 16u;
-      const uint32_t o = off < slice ? base + off : 0xfffffff0u;  // out of range: reads 0
-      warm ^= (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(urs, o, 0, 0);
-    }
-  }
+  if constexpr (!CHAIN) warm = wino_warm(urs, NOUT, KIN);
 #pragma unroll
   for (int j = 0; j < kWNT; ++j) {
     wA[j] = wfrag(1, 0, j);
@@ -383,7 +433,7 @@ conv_wino_kernel(const bf16* __restrict__ X, const bf16* __restrict__ U,
   op_store(IntC<1>{}, 0, IntC<2>{});
   op_load(IntC<1>{}, 0, IntC<3>{});
   op_store(IntC<1>{}, 0, IntC<3>{});
-  asm volatile("" ::"v"(warm));  // (the warming loads are not dead)
+  if constexpr (!CHAIN) asm volatile("" ::"v"(warm));  // (the warming loads are not dead)
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
@@ -471,6 +521,9 @@ conv_wino_kernel(const bf16* __restrict__ X, const bf16* __restrict__ U,
 
   // ---- epilogue: bias (+ ReLU) -> bf16 image [pair][column][channel] in LDS, then whole
   // 384-byte pixel rows out with the dgrad mask applied
+  // (CHAIN: the next layer's weights start towards L2 now; the word is kept until the image is
+  // written, so nothing waits for them before)
+  if constexpr (CHAIN) warm = wino_warm(wino_rsrc(Unext, 12L * NOUT * KIN * 2), NOUT, KIN);
   __syncthreads();
 #pragma unroll
   for (int j = 0; j < kWNT; ++j) {
@@ -494,6 +547,7 @@ conv_wino_kernel(const bf16* __restrict__ X, const bf16* __restrict__ U,
       *reinterpret_cast<bf16x4*>(lds + (2 * m + 1) * kEpRow + n) = ob;
     }
   }
+  if constexpr (CHAIN) asm volatile("" ::"v"(warm));
   __syncthreads();
   if constexpr (BNM != 0) {
     // one board: 16 consecutive threads own one pixel row of 128 channels (512 = 32 rows per
@@ -584,8 +638,71 @@ conv_wino_kernel(const bf16* __restrict__ X, const bf16* __restrict__ U,
       *reinterpret_cast<bf16x8*>(Y + (size_t)((b * WO + i + HO) * WO + j + HO) * YC + n0 + k8) = v;
     }
   }
+}
+
+template <int WN, bool SINGLE, int PAIRS = kWP, int BNM = 0>
+__global__ void __launch_bounds__(512, 1)
+conv_wino_kernel(const bf16* __restrict__ X, const bf16* __restrict__ U,
+                 const float* __restrict__ bias, bf16* __restrict__ Y,
+                 const bf16* __restrict__ mask, int B, int S, int KIN, int NOUT, int HO, int YC,
+                 int relu, int HM, int nb, WgradRed red, WinoBN bn = WinoBN{}) {
+  using T = WinoTile<WN, PAIRS>;
+  // + a [2][64] float column-statistics accumulator past the loop ring / epilogue image
+  __shared__ __attribute__((aligned(16))) bf16 lds[T::Lds + (BNM ? 256 : 0)];
+  if constexpr (BNM != 0) {
+    float* sred = reinterpret_cast<float*>(lds + T::Lds);
+    if (bn.spart && threadIdx.x < 128) sred[threadIdx.x] = 0.f;  // published by the first barrier
+  }
+  const auto urs = wino_rsrc(U, 12L * NOUT * KIN * 2);
+  const auto g = wino_geom<WN, SINGLE, PAIRS>(B, S, nb);
+  wino_layer<WN, SINGLE, PAIRS, BNM, false>(urs, lds, g, X, bias, Y, mask, B, S, KIN, NOUT, HO,
+                                            YC, relu, HM, nb, bn, nullptr);
   // a deferred wgrad reduction riding in this launch (every block claims units of it)
   if (red.ticket) wslab_reduce_dynamic<kRedU>(red, reinterpret_cast<int*>(lds));
+}
+
+// A chain of up to kChainMax layers of one width (KIN == NOUT == WN, halo 1 everywhere) in one
+// launch: act[l] -> act[l + 1] with weights U[l], bias[l] (or null) and ReLU where bit l of
+// `relu` is set. A block owns whole boards and all output channels, and a layer reads raw rows
+// of the block's own boards only (plus one row past them: the next board's zero halo, which no
+// layer writes), so layer l + 1 of a board needs layer l of that board and nothing else: the
+// block loops over the layers with block-local synchronisation, no grid barrier. By value in
+// the kernel arguments, the table stays in SGPRs.
+// The L + 1 activation buffers must be pairwise distinct (the host entry checks): a buffer is
+// then never loaded in the launch before this block stored it, so no stale line of it can sit
+// in the CU's L1.
+constexpr int kChainMax = 16;
+struct WinoChain {
+  bf16* act[kChainMax + 1];
+  const bf16* U[kChainMax];
+  const float* bias[kChainMax];
+  uint32_t relu;
+  int L;
+};
+template <int WN, bool SINGLE>
+__global__ void __launch_bounds__(512, 1)
+conv_wino_chain_kernel(WinoChain c, int B, int S, int nb) {
+  using T = WinoTile<WN, kWP>;
+  __shared__ __attribute__((aligned(16))) bf16 lds[T::Lds];
+  const auto g = wino_geom<WN, SINGLE, kWP>(B, S, nb);
+  // the first layer's weights towards L2 (every later layer's: during the layer before it)
+  const uint32_t warm = wino_warm(wino_rsrc(c.U[0], 12L * WN * WN * 2), WN, WN);
+  asm volatile("" ::"v"(warm));
+#pragma unroll 1
+  for (int l = 0; l < c.L; ++l) {
+    const int ln = l + 1 < c.L ? l + 1 : l;  // (the last layer warms its own weights: a dummy)
+    wino_layer<WN, SINGLE, kWP, 0, true>(wino_rsrc(c.U[l], 12L * WN * WN * 2), lds, g, c.act[l],
+                                         c.bias[l], c.act[l + 1], nullptr, B, S, WN, WN, 1, WN,
+                                         (int)((c.relu >> l) & 1u), 1, nb, WinoBN{}, c.U[ln]);
+    // Layer boundary: the block's output stores retired and released to the workgroup, one
+    // barrier, an acquire, and only then the next layer's first raw-row load. The same barrier
+    // keeps the next layer's V(0) (op_store) off the epilogue image, which aliases the V ring,
+    // until every thread has read its part of the image.
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __syncthreads();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  }
 }
 
 // Winograd weights of 3x3 layers from the fp32 OIHW masters (pack.h wino_pack_block: table
@@ -781,6 +898,50 @@ int rag_conv_wino_bn_launch(const void* X, const void* W, const float* bias, voi
     conv_wino_kernel<128, true, kWP, 2><<<B, 512, 0, stream>>>(
         (const bf16*)X, (const bf16*)W, bias, (bf16*)Y, (const bf16*)mask, B, S, KIN, NOUT, HO,
         YC, relu, HM, 1, r, WinoBN{mcoef, nullptr, spart, smean});
+  return (int)hipGetLastError();
+}
+
+// A run of consecutive forward layers in one launch (conv_wino_chain_kernel). table: host int64
+// [L][7] = (X, U, bias or 0, Y, relu, KIN, NOUT) per layer, every activation with halo 1 and
+// its layer's channel count. -1 unless: 1 <= L <= 16; every layer passes rag_conv_wino_ok; all
+// channel counts are equal and one block spans them (a one-dimensional grid); X of layer l + 1
+// is Y of layer l; the L + 1 activation buffers do not overlap pairwise (the kernel's comment);
+// and wino_mode(B, ...) == 1, i.e. the single launches would run the same one-board blocks --
+// except with `any_batch`, which drops that last condition alone (tests and benchmarks at
+// batches the selector gives to another kernel, as rag_conv_wino's `half` overrides it).
+RAG_API int rag_conv_wino_chain(const int64_t* table, int L, int B, int S, hipStream_t stream,
+                                int any_batch) {
+  constexpr int kF = 7;
+  if (!table || L < 1 || L > kChainMax || B <= 0) return -1;
+  const int C = (int)table[5];
+  if (!rag_conv_wino_ok(S, 1, C, C, 3) || wino_tile(C, S) != C) return -1;
+  if (!any_batch && wino_mode(B, S, C, C) != 1) return -1;
+  WinoChain c{};
+  c.L = L;
+  for (int l = 0; l < L; ++l) {
+    const int64_t* r = table + (size_t)l * kF;
+    if (r[5] != C || r[6] != C || !r[0] || !r[1] || !r[3]) return -1;
+    if (l > 0 && r[0] != table[(size_t)(l - 1) * kF + 3]) return -1;
+    c.act[l] = reinterpret_cast<bf16*>(r[0]);
+    c.act[l + 1] = reinterpret_cast<bf16*>(r[3]);
+    c.U[l] = reinterpret_cast<const bf16*>(r[1]);
+    c.bias[l] = reinterpret_cast<const float*>(r[2]);
+    if (r[4]) c.relu |= 1u << l;
+  }
+  const int64_t bytes = (int64_t)B * (S + 2) * (S + 2) * C * 2;
+  for (int i = 0; i <= L; ++i)
+    for (int j = 0; j < i; ++j) {
+      const int64_t d = reinterpret_cast<int64_t>(c.act[i]) - reinterpret_cast<int64_t>(c.act[j]);
+      if ((d < 0 ? -d : d) < bytes) return -1;
+    }
+  const int nb = wino_boards_per_block(S);
+  const dim3 grid((B + nb - 1) / nb);
+  if (C == 128)
+    conv_wino_chain_kernel<128, true><<<grid, 512, 0, stream>>>(c, B, S, nb);
+  else if (nb == 1)
+    conv_wino_chain_kernel<192, true><<<grid, 512, 0, stream>>>(c, B, S, nb);
+  else
+    conv_wino_chain_kernel<192, false><<<grid, 512, 0, stream>>>(c, B, S, nb);
   return (int)hipGetLastError();
 }
 

@@ -50,6 +50,8 @@ RAG_API int rag_pack_nchw(const float* in, void* X, int B, int C, int S, int H, 
 RAG_API int rag_conv_wino_ok(int S, int HI, int KIN, int NOUT, int KS);
 RAG_API int rag_conv_wino_mode(int B, int S, int KIN, int NOUT);
 RAG_API int rag_conv_wino_bn_ok(int B, int S, int KIN, int NOUT);
+RAG_API int rag_conv_wino_chain(const int64_t* table, int L, int B, int S, hipStream_t stream,
+                                int any_batch);
 RAG_API int rag_wino_pack(const int64_t* table, int nlayers, int max_tiles, hipStream_t stream,
                           int64_t goff, float lr, float wd, int sgd_on);
 RAG_API int rag_pack_step(const int64_t* wtable, int nwino, const int64_t* ttable, int nrows,

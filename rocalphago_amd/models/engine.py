@@ -236,6 +236,9 @@ class HipTrunk(_PackedConvs):
     # wgrad slab reductions ride along the next dgrad launch (False: their own reduce kernels,
     # and the dgrads of the Winograd layers run Winograd too)
     DEFER_REDUCE = True
+    # every maximal run of consecutive one-board Winograd forward layers of one width is one
+    # launch (ops.conv_wino_chain; False: one launch per layer, the A/B)
+    WINO_CHAIN = True
 
     def __init__(self, specs, board, device):
         assert specs, "empty trunk"
@@ -258,6 +261,8 @@ class HipTrunk(_PackedConvs):
         # half-board Winograd blocks at every batch (a search whose GPU rollouts share the chip
         # may set it)
         self.wino_half = False
+        self.wino_chain = self.WINO_CHAIN
+        self._chain_plans = {}
         self._work = None
         self.defer_reduce = self.DEFER_REDUCE
         # The dgrad of a Winograd layer runs the direct kernel while it carries a deferred
@@ -342,12 +347,44 @@ class HipTrunk(_PackedConvs):
             self._direct_layouts()
         return plan
 
+    def chain_plan(self, B):
+        """{first layer: layer past the last} of every maximal run of two or more consecutive
+        layers that one conv_wino_chain launch runs at batch B: Winograd layers in one-board
+        blocks (conv_wino_mode 1), one width in and out, halo 1 on both sides."""
+        runs = self._chain_plans.get(B)
+        if runs is None:
+            wino = self.wino_plan(B)
+            ok = [bool(wino[l]) and s.cinp == s.coutp and self.halo[l] == 1
+                  and self.halo[l + 1] == 1
+                  and ops.conv_wino_mode(B, self.S, s.cinp, s.coutp) == 1
+                  for l, s in enumerate(self.specs)]
+            runs, l = {}, 0
+            while l < self.L:
+                e = l
+                while e < self.L and ok[e] and self.specs[e].cinp == self.specs[l].cinp \
+                        and e - l < 16:
+                    e += 1
+                if e - l >= 2:
+                    runs[l] = e
+                l = max(e, l + 1)
+            self._chain_plans[B] = runs
+        return runs
+
     def forward(self, B, training=False):
         S = self.S
         wino = self.wino_plan(B)
+        runs = self.chain_plan(B) if self.wino_chain and not self.wino_half else {}
+        skip = 0
         for l, s in enumerate(self.specs):
+            if l < skip:
+                continue
             x, y = self.acts[l][:B], self.acts[l + 1][:B]
-            if wino[l]:
+            if l in runs:
+                skip = runs[l]
+                ops.conv_wino_chain([(self.acts[k][:B], self._uf[k], self._bias[k],
+                                      self.acts[k + 1][:B], self.specs[k].relu)
+                                     for k in range(l, skip)], B, S)
+            elif wino[l]:
                 ops.conv_wino(x, self._uf[l], self._bias[l], y, B, S, s.cinp, s.coutp,
                               self.halo[l + 1], s.relu, half=self.wino_half)
             else:

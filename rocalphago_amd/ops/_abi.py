@@ -29,6 +29,7 @@ SIGNATURES = {
     "rag_conv_wino_mode": [I, I, I, I],
     "rag_conv_wino_bn_ok": [I, I, I, I],
     "rag_conv_wino_bn": [P] * 6 + [I] * 8 + [P] * 6,
+    "rag_conv_wino_chain": [P, I, I, I, P, I],
     "rag_pack_input_u8": [P, P, P, P, I, I, I, I, I, I, P],
     "rag_pack_input_f32": [P, P, P, P, I, I, I, I, I, I, P],
     "rag_pack_input_bits": [P, P, P, P, I, I, I, I, I, P],

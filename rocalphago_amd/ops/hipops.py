@@ -241,6 +241,27 @@ def conv_wino(x, u, bias, y, B, S, kin, nout, ho, relu, mask=None, mask_halo=Non
     return y
 
 
+def conv_wino_chain(layers, B, S, any_batch=False):
+    """A run of consecutive forward conv_wino layers of one width in ONE launch
+    (conv_wino_chain_kernel, csrc/hip/conv_wino.hip): every block runs all the layers of its own
+    boards. ``layers``: (x, u, bias or None, y, relu) per layer, at most 16, each x the previous
+    layer's y, every activation with halo 1, and the L + 1 activation buffers distinct memory.
+    Bit-identical to the same layers through conv_wino one launch at a time. Refused (an error,
+    nothing launched) unless conv_wino_mode(B, ...) == 1; ``any_batch`` drops that one condition
+    (tests and benchmarks at batches the selector gives to another kernel)."""
+    rows = []
+    for x, u, bias, y, relu in layers:
+        _index_range_ok(x, y)
+        if x.shape[1] != S + 2 or y.shape[1] != S + 2:
+            raise ValueError("conv_wino_chain activations must have halo 1")
+        rows.append((x.data_ptr(), u.data_ptr(), 0 if bias is None else bias.data_ptr(),
+                     y.data_ptr(), int(bool(relu)), x.shape[-1], y.shape[-1]))
+    table = (ctypes.c_int64 * (7 * len(rows)))(*[v for r in rows for v in r])
+    _check(_lib().rag_conv_wino_chain(table, len(rows), B, S, _stream(), int(bool(any_batch))),
+           "conv_wino_chain")
+    return layers[-1][3] if layers else None
+
+
 def conv_wino_bn_ok(B, S, kin, nout):
     """True if conv_wino_bn (the Winograd kernel with the residual trunk's fused BatchNorm) runs
     a batch of B: 128 -> 128 channels, one board per block, a grid that fills the chip."""

@@ -157,9 +157,18 @@ class _SlotResult(object):
 class NetworkEvaluator(object):
     """Batched leaf evaluation: native boards -> (move priors [n, S*S], values [n])."""
 
-    def __init__(self, policy=None, value=None, nthreads=8, two_streams=True, graph=False):
+    def __init__(self, policy=None, value=None, nthreads=8, two_streams=True, graph=False,
+                 wino_chain=False):
         self.policy = policy
         self.value = value
+        # HipTrunk.wino_chain of this evaluator's plans (None: left as the trunks have it). Off
+        # in the search: a chain block holds its CU for the whole run of layers (~0.5 ms)
+        # instead of ~50 us, and the GPU rollout slices that share the chip no longer slip in
+        # between the layers: 127.0 / 138.2 / 137.1k sims/s with the chain against 140.8 /
+        # 140.1 / 141.6k without (profiles/wino_chain_ab.txt). Training keeps it on (the
+        # attribute lives on the plan's trunk: a model trained through the very plan its
+        # evaluator uses follows the evaluator from then on).
+        self.wino_chain = wino_chain
         # policy and value trunks of a wave on two streams (two_streams=False: one): 95.4k vs
         # 92.8k sims/s, profiles/mcts_eval_streams_r2.txt
         self.two_streams = bool(two_streams)
@@ -431,6 +440,10 @@ class NetworkEvaluator(object):
             pv = self.value.model._plan_for() if self.value is not None else None
             ok = (self.policy is None or pp is not None) and (self.value is None or pv is not None)
             self._plan_cache = (pp, pv) if ok else None
+            if self.wino_chain is not None:
+                for plan in (pp, pv):
+                    if plan is not None and hasattr(plan.trunk, "wino_chain"):
+                        plan.trunk.wino_chain = bool(self.wino_chain)
             net = self.value if self.shared or self.policy is None else self.policy
             fl = net.preprocessor.feature_list if net is not None else []
             self._sens_off = None
