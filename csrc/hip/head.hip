@@ -7,7 +7,8 @@
 // max/sum reductions, then probabilities, per-sample loss, dL/dz and top-1 hit written in the same
 // pass. Loss modes: 0 = none (inference), 1 = categorical cross-entropy (Keras, mean over batch),
 // 2 = REINFORCE log_loss (Keras: -y log clip(p), averaged over the S*S classes and the batch;
-// reinforcement_policy_trainer.py:89-94), each sample scaled by an optional signed weight.
+// reinforcement_policy_trainer.py:89-94), each sample scaled by an optional signed weight. A board
+// whose label probability is clipped has the clipped loss and a zero gradient.
 #include "common.h"
 #include "rag_api.h"
 
@@ -104,11 +105,20 @@ policy_head_fwd_kernel(const bf16* __restrict__ H, const float* __restrict__ w, 
   const int64_t lab = (mode && labels) ? labels[b] : -1;
   const float sw = sweight ? sweight[b] : 1.f;
   const float cls = (mode == 2) ? 1.f / (float)C : 1.f;
+  // Both objectives clip the label probability to [1e-7, 1 - 1e-7] before the log (Keras
+  // epsilon), and autograd through that clamp gives a board whose label probability lies
+  // outside the range no gradient at all: its dz, dpass and dzsum are zero, as in the generic
+  // executor (docs/PARITY.md Q16). Block-uniform: every thread reads the same z[lab].
+  bool clipped = false;
+  if (mode && lab >= 0) {
+    const float pl = __expf(z[lab] - gmax) * inv;
+    clipped = pl < 1e-7f || pl > 1.f - 1e-7f;
+  }
   // dL/d(pass logit): it also flows back into every position logit through W
   float dp = 0.f;
   if (has_pass) {
     const float pp = __expf(z[S2] - gmax) * inv;
-    dp = (pp - (lab == S2 ? 1.f : 0.f)) * sw * cls * gscale;
+    dp = clipped ? 0.f : (pp - (lab == S2 ? 1.f : 0.f)) * sw * cls * gscale;
     if (threadIdx.x == 0) {
       probs[(size_t)b * C + S2] = pp;
       if (mode && dpass) dpass[b] = dp;
@@ -120,7 +130,8 @@ policy_head_fwd_kernel(const bf16* __restrict__ H, const float* __restrict__ w, 
     probs[(size_t)b * C + p] = pr;
     if (mode && dz) {
       const float y = (p == lab) ? 1.f : 0.f;
-      const float d = (pr - y) * sw * cls * gscale + (has_pass ? dp * pass_w[p] : 0.f);
+      const float d =
+          clipped ? 0.f : (pr - y) * sw * cls * gscale + (has_pass ? dp * pass_w[p] : 0.f);
       dz[(size_t)b * S2 + p] = d;
       dsum += d;
     }
