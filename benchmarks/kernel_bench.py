@@ -83,6 +83,12 @@ def main():
     t = timeit(lambda: ops.policy_head_fwd(h, wv, b0, pb, probs, K, labels=lab, loss=loss, dz=dz,
                                            mode=1, gscale=1.0 / B))
     res.append(("policy_head_fwd", K, 1, 1, t, 0.0))
+    # the same head on dense targets (visit distributions over ~40 points), same outputs
+    tg = torch.rand(B, S * S, device=dev) * (torch.rand(B, S * S, device=dev) < 40.0 / (S * S))
+    tg = (tg / tg.sum(1, keepdim=True).clamp_min(1e-9)).contiguous()
+    t = timeit(lambda: ops.policy_head_soft(h, wv, b0, pb, probs, K, tg, loss=loss, dz=dz,
+                                            gscale=1.0 / B))
+    res.append(("policy_head_soft", K, 1, 1, t, 0.0))
     dh = ops.alloc_padded(B, S, 1, K, dev)
     dwv = torch.zeros(K, device=dev)
     t = timeit(lambda: ops.head_bwd(h, wv, dz, dh, dwv, b0, pb, K))

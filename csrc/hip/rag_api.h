@@ -76,6 +76,12 @@ RAG_API int rag_policy_head_fwd(const void* H, const float* w, const float* b0,
                                 float* loss, float* dz, float* hit, float* zout, float* dpass,
                                 float* acc, float* dzsum, int B, int S, int KP, int K, int mode,
                                 float gscale, hipStream_t stream);
+RAG_API int rag_policy_head_soft(const void* H, const float* w, const float* b0,
+                                 const float* pbias, const float* pass_w, const float* pass_b,
+                                 float* probs, const float* targets, const float* sweight,
+                                 float* loss, float* dz, float* hit, float* zout, float* dpass,
+                                 float* dzsum, int B, int S, int KP, int K, float gscale,
+                                 hipStream_t stream);
 RAG_API int rag_head_bwd(const void* H, const float* w, const float* dz, void* dH, float* dw,
                          float* db0, float* dpbias, float* work, int B, int S, int KP, int K,
                          int relu_mask, const float* mloss, const float* mhit, float* acc,
@@ -98,6 +104,10 @@ RAG_API int rag_value_mlp_bwd(const float* z, const float* W1, const float* W2, 
 RAG_API int rag_sl_batch(const int64_t* index, const int64_t* labels, const int64_t* tf_table,
                          int P, const int* sym, int nsym, unsigned seed, unsigned step,
                          int* tf_out, int64_t* lab_out, int B, hipStream_t stream);
+RAG_API int rag_sl_batch_soft(const int64_t* index, const uint16_t* visits, int CD,
+                              const int64_t* tf_table, int P, const int* sym, int nsym,
+                              unsigned seed, unsigned step, int* tf_out, float* targets_out,
+                              int C, int B, hipStream_t stream);
 RAG_API int rag_value_batch(const int64_t* index, const float* values, const int* sym, int nsym,
                             unsigned seed, unsigned step, int* tf_out, float* y_out, int B,
                             hipStream_t stream);

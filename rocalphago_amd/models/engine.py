@@ -764,8 +764,10 @@ class PolicyHeadEngine(object):
         self._B = B
 
     def forward(self, B, w, b0, pbias, labels=None, sweight=None, mode=0, gscale=1.0,
-                pass_params=None, acc=None):
-        """pass_params: (W [S*S], b [1]) of a PassLogit layer, or None. acc: fp32 [2] running
+                pass_params=None, acc=None, targets=None):
+        """pass_params: (W [S*S], b [1]) of a PassLogit layer, or None. targets: dense fp32
+        [B, C] targets instead of ``labels`` (categorical cross-entropy, mode 1 only: the soft
+        head kernel). acc: fp32 [2] running
         (loss sum, hit count). In a training forward (mode > 0) the sums are added by the
         matching backward() (its reduce launch sums the per-board loss / hit arrays), so every
         training forward that passes ``acc`` must be followed by backward() before the next
@@ -773,6 +775,8 @@ class PolicyHeadEngine(object):
         if mode and acc is not None and getattr(self, "_macc", None) is not None:
             raise RuntimeError("PolicyHeadEngine: training forward with acc= while the previous "
                                "one's metrics are still pending (backward() not called)")
+        if targets is not None and (labels is not None or mode != 1):
+            raise ValueError("PolicyHeadEngine: targets= excludes labels= and needs mode 1")
         self.ensure(B)
         h = self.trunk.output(B)
         pk = {}
@@ -783,11 +787,18 @@ class PolicyHeadEngine(object):
         # (acc in the forward kernel meant two contended device atomics per board)
         # (set only once the launch succeeded: a failed forward leaves nothing pending)
         self._macc = None
-        ops.policy_head_fwd(h, w, b0, pbias, self.probs[:B], self.K, labels=labels,
-                            sweight=sweight, loss=self.loss[:B] if mode else None,
-                            dz=self.dz[:B] if mode else None, hit=self.hit[:B] if mode else None,
-                            mode=mode, gscale=gscale, acc=None if mode else acc,
-                            dzsum=self.dzsum[:B] if (mode and not pk) else None, **pk)
+        if targets is not None:
+            ops.policy_head_soft(h, w, b0, pbias, self.probs[:B], self.K, targets,
+                                 sweight=sweight, loss=self.loss[:B], dz=self.dz[:B],
+                                 hit=self.hit[:B], gscale=gscale,
+                                 dzsum=None if pk else self.dzsum[:B], **pk)
+        else:
+            ops.policy_head_fwd(h, w, b0, pbias, self.probs[:B], self.K, labels=labels,
+                                sweight=sweight, loss=self.loss[:B] if mode else None,
+                                dz=self.dz[:B] if mode else None,
+                                hit=self.hit[:B] if mode else None, mode=mode, gscale=gscale,
+                                acc=None if mode else acc,
+                                dzsum=self.dzsum[:B] if (mode and not pk) else None, **pk)
         self._macc = acc if mode else None
         self._dzsum = bool(mode and not pk)
         return self.probs[:B]

@@ -185,28 +185,36 @@ class PolicyPlan(_TrunkPlan):
         mode = self.loss_mode(loss)
         if mode is None:
             return None
+        targets = None
         if labels is None:
-            # one-hot targets only (the reference's CE / REINFORCE targets); else generic path
-            if not bool(((y.sum(1) == 1) & (y.max(1).values == 1)).all()):
+            # one-hot targets (the reference's CE / REINFORCE targets) go through the label
+            # kernel; dense ones (visit distributions) through the soft head under categorical
+            # cross-entropy, and through the generic path under any other loss
+            if bool(((y.sum(1) == 1) & (y.max(1).values == 1)).all()):
+                labels = y.argmax(1)
+            elif loss == "categorical_crossentropy":
+                targets = y.float().contiguous()
+            else:
                 return None
-            labels = y.argmax(1)
         B = self.prepare(x, index, transforms)
         norm = 1.0
         if sw is not None:
             norm = float((sw != 0).float().mean().clamp_min(1e-12))
-        self.fwd_bwd(B, labels, sw, mode, 1.0 / (B * norm))
+        self.fwd_bwd(B, labels, sw, mode, 1.0 / (B * norm), targets=targets)
         lossv = float(self.head.loss[:B].mean()) / norm
         acc = float(self.head.hit[:B].mean()) if want_acc else None
         return lossv, acc
 
-    def fwd_bwd(self, B, labels, sw, mode, gscale, on_layer_grads=None, metrics=None):
+    def fwd_bwd(self, B, labels, sw, mode, gscale, on_layer_grads=None, metrics=None,
+                targets=None):
         """Forward + fused loss + full backward into net.flat_grad (no host syncs). metrics:
-        fp32 [2] device accumulator of (loss sum, top-1 hits), updated in the head kernel."""
+        fp32 [2] device accumulator of (loss sum, top-1 hits), updated in the head kernel.
+        targets: dense fp32 [B, C] targets in place of ``labels`` (mode 1 only)."""
         self.trunk.forward(B, training=True)
         w, b0 = self.head_params()
         pb = self.net.params_of(self.bias_name)[0]
         self.head.forward(B, w, b0, pb, labels=labels, sweight=sw, mode=mode, gscale=gscale,
-                          pass_params=self._pass_params(), acc=metrics)
+                          pass_params=self._pass_params(), acc=metrics, targets=targets)
         try:
             if self.pass_name:
                 dW, db = self.net.grads_of(self.pass_name)

@@ -37,6 +37,7 @@ SIGNATURES = {
     "rag_pack_nchw": [P, P, I, I, I, I, I, P],
     # head.hip
     "rag_policy_head_fwd": [P] * 16 + [I, I, I, I, I, F, P],
+    "rag_policy_head_soft": [P] * 15 + [I, I, I, I, F, P],
     "rag_head_bwd": [P] * 8 + [I] * 5 + [P] * 5,
     "rag_head_bwd_workspace": [I, I, I],
     "rag_head_linear": [P, P, P, P, I, I, I, I, P],
@@ -44,6 +45,7 @@ SIGNATURES = {
     "rag_value_mlp_workspace": [I, I],
     "rag_value_mlp_bwd": [P] * 16 + [I, I, I, I, P],
     "rag_sl_batch": [P, P, P, I, P, I, C.c_uint, C.c_uint, P, P, I, P],
+    "rag_sl_batch_soft": [P, P, I, P, I, P, I, C.c_uint, C.c_uint, P, P, I, I, P],
     "rag_value_batch": [P, P, P, I, C.c_uint, C.c_uint, P, P, I, P],
     "rag_value_mlp_bwd_workspace": [I, I],
     # optim.hip

@@ -518,6 +518,27 @@ def policy_head_fwd(h, w, b0, pbias, probs, K, labels=None, sweight=None, loss=N
         _ptr(acc), _ptr(dzsum), B, S, KP, K, mode, float(gscale), _stream()), "policy_head_fwd")
 
 
+def policy_head_soft(h, w, b0, pbias, probs, K, targets, sweight=None, loss=None, dz=None,
+                     hit=None, gscale=1.0, pass_w=None, pass_b=None, zout=None, dpass=None,
+                     dzsum=None):
+    """policy_head_fwd under categorical cross-entropy on dense ``targets`` (fp32 [B, C],
+    C = S*S, + 1 with ``pass_w``/``pass_b``, pass last; used as given, not renormalised):
+    probabilities, per-board loss, dL/dz, argmax-agreement hit (head.hip
+    policy_head_soft_kernel)."""
+    B, WP, _, KP = h.shape
+    S = WP - 2
+    C = S * S + (1 if pass_w is not None else 0)
+    if pass_w is not None and dzsum is not None:
+        raise ValueError("policy_head_soft: dzsum has no pass-logit form")
+    if (targets is None or tuple(targets.shape) != (B, C) or targets.dtype != torch.float32
+            or not targets.is_contiguous()):
+        raise ValueError("policy_head_soft: targets must be contiguous fp32 [%d, %d]" % (B, C))
+    _check(_lib().rag_policy_head_soft(
+        _ptr(h), _ptr(w), _ptr(b0), _ptr(pbias), _ptr(pass_w), _ptr(pass_b), _ptr(probs),
+        _ptr(targets), _ptr(sweight), _ptr(loss), _ptr(dz), _ptr(hit), _ptr(zout), _ptr(dpass),
+        _ptr(dzsum), B, S, KP, K, float(gscale), _stream()), "policy_head_soft")
+
+
 def pass_grads(zout, dpass, dW, db):
     """PassLogit weight gradients on the GPU: dW = dpass^T zout ([S*S]), db = sum(dpass)."""
     B, P = zout.shape
@@ -616,6 +637,36 @@ def sl_batch(index, labels, tf_table, sym, seed, step, tf_out=None, lab_out=None
                                ctypes.c_uint(step & 0xFFFFFFFF), _ptr(tf_out), _ptr(lab_out), B,
                                _stream()), "sl_batch")
     return tf_out, lab_out
+
+
+def sl_batch_soft(index, visits, tf_table, sym, seed, step, classes, tf_out=None,
+                  targets_out=None):
+    """sl_batch for visit-count targets (batch.hip): the same transform per sampled row
+    (int32 [B]) and the row's counts (uint16 [N, S*S] or [N, S*S + 1], pass last) normalised and
+    moved through the transform into fp32 [B, classes] (classes = S*S or S*S + 1)."""
+    B = index.numel()
+    dev = index.device
+    for t, dt in ((index, torch.int64), (visits, torch.uint16), (tf_table, torch.int64),
+                  (sym, torch.int32)):
+        if t.dtype != dt or not t.is_contiguous():
+            raise ValueError("sl_batch_soft: bad dtype / layout")
+    P = tf_table.shape[1]
+    if visits.dim() != 2 or visits.shape[1] not in (P, P + 1) or classes not in (P, P + 1):
+        raise ValueError("sl_batch_soft: visits [N, %d (+1)] and %d (+1) classes expected" %
+                         (P, P))
+    if tf_out is None:
+        tf_out = torch.empty(B, dtype=torch.int32, device=dev)
+    if targets_out is None:
+        targets_out = torch.empty((B, classes), dtype=torch.float32, device=dev)
+    elif (tuple(targets_out.shape) != (B, classes) or targets_out.dtype != torch.float32
+          or not targets_out.is_contiguous()):
+        raise ValueError("sl_batch_soft: targets_out must be contiguous fp32 [B, classes]")
+    _check(_lib().rag_sl_batch_soft(_ptr(index), _ptr(visits), visits.shape[1], _ptr(tf_table),
+                                    P, _ptr(sym), sym.numel(),
+                                    ctypes.c_uint(seed & 0xFFFFFFFF),
+                                    ctypes.c_uint(step & 0xFFFFFFFF), _ptr(tf_out),
+                                    _ptr(targets_out), classes, B, _stream()), "sl_batch_soft")
+    return tf_out, targets_out
 
 
 def value_batch(index, values, sym, seed, step, tf_out=None, y_out=None):

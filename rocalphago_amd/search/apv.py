@@ -774,6 +774,12 @@ class ParallelMCTS(object):
         """(moves, visits, Q, prior) of the root children."""
         return self._search.root_stats()
 
+    def reset(self):
+        """Drop the tree: the next search starts from an empty root (training/search_data.py
+        records the visit counts of one search alone)."""
+        self._search = None
+        self._history = None
+
     def update_with_move(self, last_move):
         s = self._search
         if s is None:

@@ -47,10 +47,44 @@ def apply_transform_np(planes, t):
     return np.stack([fn(p) for p in planes])
 
 
-class DeviceDataset(object):
-    """uint8 states [N, F, S, S] + flat action labels [N] resident on ``device``."""
+def _visits_array(visits, n, S):
+    """uint16 [N, S*S] or [N, S*S + 1] (pass last) visit counts, validated."""
+    v = np.ascontiguousarray(visits)
+    if v.ndim != 2 or v.shape[0] != n or v.shape[1] not in (S * S, S * S + 1):
+        raise ValueError("visits must be [%d, %d] or [%d, %d], got %s" %
+                         (n, S * S, n, S * S + 1, v.shape))
+    if v.dtype != np.uint16:
+        if v.size and (v.min() < 0 or v.max() > 65535):
+            raise ValueError("visit counts must fit uint16")
+        v = v.astype(np.uint16)
+    return v
 
-    def __init__(self, states, actions, device, board=None):
+
+def soft_targets_np(visits, tf, table, classes):
+    """Host definition of ops.sl_batch_soft: visit rows [B, CD] -> float32 targets
+    [B, classes], normalised over the columns the model has a class for (a stored pass count
+    without a pass class is dropped first; a pass class without a stored count gets 0) and
+    moved through ``table[tf]``; a zero-sum row stays all zero."""
+    v = np.asarray(visits, dtype=np.float64)
+    B, CD = v.shape
+    P = table.shape[1]
+    n = min(CD, classes)
+    s = v[:, :n].sum(1, keepdims=True)
+    q = np.divide(v[:, :n], s, out=np.zeros((B, n)), where=s > 0)
+    Y = np.zeros((B, classes), np.float32)
+    rows = np.arange(B)[:, None]
+    Y[rows, np.asarray(table)[np.asarray(tf)]] = q[:, :P]
+    if n > P:
+        Y[:, P] = q[:, P]
+    return Y
+
+
+class DeviceDataset(object):
+    """uint8 states [N, F, S, S] + flat action labels [N] resident on ``device``; optionally
+    ``visits``: uint16 search visit counts [N, S*S] or [N, S*S + 1] (pass last), the dense policy
+    targets of ``--targets visits``."""
+
+    def __init__(self, states, actions, device, board=None, visits=None):
         states = np.asarray(states)
         self.N, self.F, self.S = states.shape[0], states.shape[1], states.shape[-1]
         acts = np.asarray(actions).astype(np.int64)
@@ -60,14 +94,22 @@ class DeviceDataset(object):
             self.device)
         self.labels = torch.from_numpy(labels).to(self.device)
         self.tf_table = torch.from_numpy(label_transform_table(self.S)).to(self.device)
+        self._set_visits(visits)
+
+    def _set_visits(self, visits):
+        self.visits = None
+        if visits is not None:
+            self.visits = torch.from_numpy(_visits_array(visits, self.N, self.S)).to(self.device)
 
     @classmethod
     def from_hdf5(cls, h5file, device):
-        return cls(h5file["states"][()], h5file["actions"][()], device)
+        visits = h5file["visits"][()] if "visits" in h5file else None
+        return cls(h5file["states"][()], h5file["actions"][()], device, visits=visits)
 
     @classmethod
-    def synthetic(cls, n, planes, board, device, seed=0, density=0.35):
-        """Random binary planes / uniform labels generated on the device (benchmarks)."""
+    def synthetic(cls, n, planes, board, device, seed=0, density=0.35, visits=False):
+        """Random binary planes / uniform labels generated on the device (benchmarks); with
+        ``visits`` also visit rows [n, board^2 + 1]: ~40 random classes with counts below 64."""
         g = torch.Generator(device=device)
         g.manual_seed(seed)
         ds = cls.__new__(cls)
@@ -77,19 +119,40 @@ class DeviceDataset(object):
                      density).to(torch.uint8)
         ds.labels = torch.randint(0, board * board, (n,), generator=g, device=device)
         ds.tf_table = torch.from_numpy(label_transform_table(board)).to(ds.device)
+        ds.visits = None
+        if visits:
+            C = board * board + 1
+            keep = torch.rand((n, C), generator=g, device=device) < 40.0 / C
+            counts = torch.randint(1, 64, (n, C), generator=g, device=device)
+            counts = counts * keep
+            counts[torch.arange(n, device=device), ds.labels] += 64  # the move played leads
+            ds.visits = counts.to(torch.int32).to(torch.uint16)
         return ds
 
     def batch_labels(self, index, tf):
         return self.tf_table[tf, self.labels[index]]
 
-    def host_batch(self, index, tf):
-        """CPU path: (X float32 [B,F,S,S], Y one-hot [B,S*S]) materialised with numpy."""
-        idx = index.cpu().numpy()
+    def batch_targets(self, index, tf, classes=None):
+        """CPU definition of the visit targets: float32 [B, classes] (numpy)."""
+        if self.visits is None:
+            raise ValueError("this dataset holds no visits")
+        rows = self.visits.cpu().numpy()[index.cpu().numpy()]
+        return soft_targets_np(rows, tf.cpu().numpy(), self.tf_table.cpu().numpy(),
+                               classes or self.S * self.S)
+
+    def host_states(self, index):
+        return self.states.cpu().numpy()[index.cpu().numpy()]
+
+    def host_batch(self, index, tf, soft=False, classes=None):
+        """CPU path: (X float32 [B,F,S,S], Y [B,S*S]) materialised with numpy; Y one-hot at the
+        transformed label, or with ``soft`` the transformed, normalised visit row ([B, classes],
+        classes = S*S by default)."""
         tfs = tf.cpu().numpy()
-        st = self.states.cpu().numpy()
-        X = np.stack([apply_transform_np(st[i], t) for i, t in zip(idx, tfs)]).astype(
-            np.float32)
+        X = np.stack([apply_transform_np(s, t) for s, t in
+                      zip(self.host_states(index), tfs)]).astype(np.float32)
+        if soft:
+            return X, self.batch_targets(index, tf, classes)
         lab = self.batch_labels(index.to(self.device), tf.to(self.device)).cpu().numpy()
-        Y = np.zeros((len(idx), self.S * self.S), np.float32)
-        Y[np.arange(len(idx)), lab] = 1
+        Y = np.zeros((len(tfs), self.S * self.S), np.float32)
+        Y[np.arange(len(tfs)), lab] = 1
         return X, Y

@@ -16,7 +16,7 @@ uint8 path), so training reads packed positions directly.
 import numpy as np
 import torch
 
-from .data import DeviceDataset, apply_transform_np, label_transform_table
+from .data import DeviceDataset, label_transform_table
 
 
 def pack_bits(planes):
@@ -41,7 +41,7 @@ def unpack_bits(bits, nplanes):
 class PackedDataset(DeviceDataset):
     """DeviceDataset whose ``states`` are bit-packed int64 words [N, S, S]."""
 
-    def __init__(self, states, actions, device, board=None):
+    def __init__(self, states, actions, device, board=None, visits=None):
         states = np.asarray(states)
         self.N, self.F, self.S = states.shape[0], states.shape[1], states.shape[-1]
         acts = np.asarray(actions).astype(np.int64)
@@ -56,24 +56,14 @@ class PackedDataset(DeviceDataset):
             (0, self.S, self.S), dtype=torch.int64, device=self.device)
         self.labels = torch.from_numpy(labels).to(self.device)
         self.tf_table = torch.from_numpy(label_transform_table(self.S)).to(self.device)
-
-    @classmethod
-    def from_hdf5(cls, h5file, device):
-        return cls(h5file["states"][()], h5file["actions"][()], device)
+        self._set_visits(visits)
 
     @property
     def planes(self):
         return self.F
 
-    def host_batch(self, index, tf):
-        idx = index.to(self.device)
-        st = unpack_bits(self.states[idx], self.F).cpu().numpy()
-        tfs = tf.cpu().numpy()
-        X = np.stack([apply_transform_np(s, t) for s, t in zip(st, tfs)]).astype(np.float32)
-        lab = self.batch_labels(idx, tf.to(self.device)).cpu().numpy()
-        Y = np.zeros((len(st), self.S * self.S), np.float32)
-        Y[np.arange(len(st)), lab] = 1
-        return X, Y
+    def host_states(self, index):
+        return unpack_bits(self.states[index.to(self.device)], self.F).cpu().numpy()
 
 
 class ReplayBuffer(object):

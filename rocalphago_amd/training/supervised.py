@@ -95,14 +95,30 @@ def best_epoch(epochs):
     return best
 
 
+NO_VISITS = ("--targets visits needs a dataset with a 'visits' array (uint16 [N, S*S] or "
+             "[N, S*S + 1]; training/search_data.py writes one)")
+
+
 class SupervisedTrainer(object):
     """Device-resident SL loop shared by run_training and bench.py.
 
     ``step(index)`` trains on dataset rows ``index`` (device int64) with random symmetries and
-    returns device scalars (loss_sum, hit_sum) without synchronising the host."""
+    returns device scalars (loss_sum, hit_sum) without synchronising the host.
+
+    ``targets``: "actions" (the move played, one label per row) or "visits" (the dataset's
+    search visit counts, normalised: dense targets under categorical cross-entropy; the hit is
+    the agreement of the two argmaxes)."""
 
     def __init__(self, policy_model, dataset, batch_size, symmetries=None, dp=None,
-                 loss="categorical_crossentropy", seed=0, metrics=None):
+                 loss="categorical_crossentropy", seed=0, metrics=None, targets="actions"):
+        if targets not in ("actions", "visits"):
+            raise ValueError("targets must be 'actions' or 'visits'")
+        if targets == "visits" and getattr(dataset, "visits", None) is None:
+            raise ValueError(NO_VISITS)
+        if targets == "visits" and loss != "categorical_crossentropy":
+            raise ValueError("visit targets train under categorical_crossentropy only")
+        self.targets = targets
+        self.classes = int(policy_model.output_shape[-1])
         self.model = policy_model
         self.metrics = metrics  # utils.metrics.RankMetrics (optional)
         self.ds = dataset
@@ -138,20 +154,26 @@ class SupervisedTrainer(object):
         if self.plan is not None:
             # one launch for the transforms and transformed labels, seeded by (trainer seed,
             # optimizer iteration) so a resumed run draws the same transforms
-            tf, labels = ops.sl_batch(index.long().contiguous(), self.ds.labels,
-                                      self.ds.tf_table, self.sym, self.seed,
-                                      getattr(model.optimizer, "iterations", self.count))
+            it = getattr(model.optimizer, "iterations", self.count)
+            labels = dense = None
+            if self.targets == "visits":
+                tf, dense = ops.sl_batch_soft(index.long().contiguous(), self.ds.visits,
+                                              self.ds.tf_table, self.sym, self.seed, it,
+                                              self.classes)
+            else:
+                tf, labels = ops.sl_batch(index.long().contiguous(), self.ds.labels,
+                                          self.ds.tf_table, self.sym, self.seed, it)
             B = self.plan.prepare(self.ds.states, index=index, transforms=tf)
             mode = self.plan.loss_mode(self.loss)
             hook = self.bucketer.layer_done if self.bucketer else None
             # loss / hit sums accumulate in the head kernel (no per-step reduction launches)
             self.plan.fwd_bwd(B, labels, None, mode, 1.0 / B, on_layer_grads=hook,
-                              metrics=self.metric_acc)
+                              metrics=self.metric_acc, targets=dense)
             if self.bucketer:
                 self.bucketer.finish()
             model.optimizer.apply(model.net)
         else:
-            X, Y = self.ds.host_batch(index, self._transforms(n))
+            X, Y = self._host_batch(index, self._transforms(n))
             saved = model.grad_allreduce
             if self.dp is not None and self.dp.enabled:
                 model.grad_allreduce = self.dp.allreduce_mean_
@@ -165,6 +187,11 @@ class SupervisedTrainer(object):
         self.count += n
         if self.metrics is not None:
             self.metrics.step_done()
+
+    def _host_batch(self, index, tf):
+        if self.targets == "visits":
+            return self.ds.host_batch(index, tf, soft=True, classes=self.classes)
+        return self.ds.host_batch(index, tf)
 
     def pop_metrics(self):
         """(mean loss, accuracy) since the last call, averaged over all ranks."""
@@ -196,13 +223,21 @@ class SupervisedTrainer(object):
                 self.plan.trunk.forward(B)
                 w, b0 = self.plan.head_params()
                 pb = model.net.params_of(self.plan.bias_name)[0]
-                lab = self.ds.labels[idx]
-                self.plan.head.forward(B, w, b0, pb, labels=lab, mode=1, gscale=0.0)
+                if self.targets == "visits":
+                    # no augmentation: the identity transform for every row
+                    _, dense = ops.sl_batch_soft(idx.long().contiguous(), self.ds.visits,
+                                                 self.ds.tf_table, self.sym.new_zeros(1), 0, 0,
+                                                 self.classes)
+                    self.plan.head.forward(B, w, b0, pb, targets=dense, mode=1, gscale=0.0,
+                                           pass_params=self.plan._pass_params())
+                else:
+                    lab = self.ds.labels[idx]
+                    self.plan.head.forward(B, w, b0, pb, labels=lab, mode=1, gscale=0.0)
                 tot[0] += self.plan.head.loss[:B].sum()
                 tot[1] += self.plan.head.hit[:B].sum()
                 tot[2] += B
             else:
-                X, Y = self.ds.host_batch(idx, noop.new_zeros(idx.numel()))
+                X, Y = self._host_batch(idx, noop.new_zeros(idx.numel()))
                 r = model.test_on_batch(X, Y)
                 loss, acc = (r if isinstance(r, list) else (r, 0.0))
                 tot += torch.tensor([loss * len(X), acc * len(X), len(X)], device=tot.device)
@@ -230,6 +265,7 @@ def run_training(cmd_line_args=None):
     parser.add_argument("--train-val-test", help="Fraction of data to use for training/val/test. Must sum to 1. Invalid if restarting training", nargs=3, type=float, default=[0.93, .05, .02])  # noqa: E501
     parser.add_argument("--symmetries", help="Comma-separated list of transforms, subset of noop,rot90,rot180,rot270,fliplr,flipud,diag1,diag2", default='noop,rot90,rot180,rot270,fliplr,flipud,diag1,diag2')  # noqa: E501
     parser.add_argument("--seed", help="RNG seed for shuffling / symmetries", type=int, default=None)  # noqa: E501
+    parser.add_argument("--targets", help="Policy targets: actions (the move played, one-hot) or visits (the dataset's search visit counts, normalised; training/search_data.py writes them). Default: actions", choices=["actions", "visits"], default="actions")  # noqa: E501
     parser.add_argument("--dtype", help="GPU compute precision: bf16 (fused HIP kernels) or fp32 (reference precision, generic executor). Default: bf16", choices=["bf16", "fp32"], default="bf16")  # noqa: E501
     if cmd_line_args is None:
         args = parser.parse_args()
@@ -280,6 +316,9 @@ def run_training(cmd_line_args=None):
             print("Verified agreement of number of model and dataset feature planes, but cannot "
                   "verify exact match using old dataset format.")
 
+    if args.targets == "visits" and "visits" not in dataset:
+        raise ValueError(NO_VISITS)
+
     n_total_data = len(dataset["states"])
     n_train_data = int(args.train_val_test[0] * n_total_data)
     n_train_data = n_train_data - (n_train_data % args.minibatch)
@@ -303,6 +342,7 @@ def run_training(cmd_line_args=None):
                   len(meta_writer.metadata["epochs"]))
     meta_writer.metadata["training_data"] = args.train_data
     meta_writer.metadata["model_file"] = args.model
+    meta_writer.metadata["targets"] = args.targets
     meta_writer.metadata["cmd_line_args"] = meta_writer.metadata.get("cmd_line_args", [])
     meta_writer.metadata["cmd_line_args"].append(vars(args))
     meta_writer.set_model(model)
@@ -351,7 +391,7 @@ def run_training(cmd_line_args=None):
         ds = DeviceDataset.from_hdf5(dataset, dp.device)
     rank_metrics = RankMetrics(args.out_directory, dp.rank, dp.world, dp.device)
     trainer = SupervisedTrainer(model, ds, args.minibatch, symmetries, dp,
-                                seed=args.seed or 0, metrics=rank_metrics)
+                                seed=args.seed or 0, metrics=rank_metrics, targets=args.targets)
     samples_per_epoch = args.epoch_length or n_train_data
     dev_train = torch.from_numpy(np.asarray(train_indices, dtype=np.int64)).to(dp.device)
     dev_val = torch.from_numpy(np.asarray(val_indices, dtype=np.int64)).to(dp.device)
