@@ -18,11 +18,19 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 def build_search(device, filters=192, layers=12, batch=512, rollout_device="gpu",
                  rollouts_per_leaf=1, lmbda=0.5, nthreads=16, seed=1, pipeline=3,
-                 max_inflight=8, rollout_group=8):
+                 max_inflight=8, rollout_group=8, dual=False):
     from rocalphago_amd.features.preprocessing import DEFAULT_FEATURES
     from rocalphago_amd.models.policy import CNNPolicy
     from rocalphago_amd.models.value import CNNValue
     from rocalphago_amd.search.apv import ParallelMCTS
+    if dual:  # one policy-value network: one trunk pass per leaf instead of two
+        from rocalphago_amd.models.policy_value import CNNPolicyValue
+        net = CNNPolicyValue(DEFAULT_FEATURES + ["color"], board=19, filters_per_layer=filters,
+                             layers=layers, device=device, seed=seed)
+        return ParallelMCTS(net, None, lmbda=lmbda, batch=batch, rollout_device=rollout_device,
+                            rollouts_per_leaf=rollouts_per_leaf, nthreads=nthreads, seed=seed,
+                            pipeline=pipeline, max_inflight=max_inflight,
+                            rollout_group=rollout_group)
     pol = CNNPolicy(DEFAULT_FEATURES, board=19, filters_per_layer=filters, layers=layers,
                     device=device, seed=seed)
     val = CNNValue(DEFAULT_FEATURES + ["color"], board=19, filters_per_layer=filters,
@@ -224,6 +232,9 @@ def main():
                     help="playouts per leaf (1 = AlphaGo's APV-MCTS: one rollout per simulation)")
     ap.add_argument("--lmbda", type=float, default=0.5)
     ap.add_argument("--filters", type=int, default=192)
+    ap.add_argument("--dual", action="store_true",
+                    help="one random-init policy-value network (CNNPolicyValue, --filters wide) "
+                         "instead of the two networks (single-GPU search)")
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--pipeline", type=int, default=3, help="waves in flight (1 = serial)")
     ap.add_argument("--max-inflight", type=int, default=8, help="rollout waves in flight")
@@ -256,6 +267,8 @@ def main():
         apv.ParallelMCTS.eval_priority = args.eval_priority
     if args.rollout_priority is not None:
         gpu_rollout.DEFAULT_PRIORITY = args.rollout_priority
+    if args.distributed and args.dual:
+        ap.error("--dual measures the single-GPU search")
     if args.distributed:
         from rocalphago_amd.parallel.dp import DPContext
         dp = DPContext()
@@ -279,10 +292,11 @@ def main():
                 rollout_device=args.rollout_device, rollouts_per_leaf=args.rollouts_per_leaf,
                 lmbda=args.lmbda, filters=args.filters, nthreads=args.threads,
                 pipeline=args.pipeline, max_inflight=args.max_inflight,
-                rollout_group=args.rollout_group)
+                rollout_group=args.rollout_group, dual=args.dual)
     r["pipeline"] = args.pipeline
     r.update({"metric": "MCTS simulations/s (19x19 APV-MCTS, policy+value on GPU)",
-              "model": "policy 48x192x13 + value 49x192x13+FC256", "lmbda": args.lmbda})
+              "model": "policy-value 49x%dx13, two heads (FC256)" % args.filters if args.dual
+              else "policy 48x192x13 + value 49x192x13+FC256", "lmbda": args.lmbda})
     print(json.dumps({k: (round(v, 2) if isinstance(v, float) else v) for k, v in r.items()}))
 
 

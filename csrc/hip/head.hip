@@ -44,16 +44,24 @@ struct HeadSoftmax {
   int amax;
 };
 
+// DUAL (the policy-value network's shared trunk): a second 1x1 head on the same loaded channel
+// chunks, zv[b, p] = sum_k wv[k] H[b, p, k] + b0v (fp32 [B, S*S], no softmax); its weights sit
+// behind the first head's in ws (2 KP floats).
+template <bool DUAL = false>
 __device__ __forceinline__ HeadSoftmax head_logits_softmax(
     const bf16* __restrict__ H, const float* __restrict__ w, const float* b0,
     const float* __restrict__ pbias, const float* __restrict__ pass_w,
     const float* __restrict__ pass_b, float* __restrict__ zout, float* z, float* ws, float* red,
-    int S, int KP, int K) {
+    int S, int KP, int K, const float* __restrict__ wv = nullptr, const float* b0v = nullptr,
+    float* __restrict__ zv = nullptr) {
   const int b = blockIdx.x;
   const int S2 = S * S, WP = S + 2;
   for (int k = threadIdx.x; k < KP; k += blockDim.x) ws[k] = k < K ? w[k] : 0.f;
+  if constexpr (DUAL)
+    for (int k = threadIdx.x; k < KP; k += blockDim.x) ws[KP + k] = k < K ? wv[k] : 0.f;
   __syncthreads();
   const float bias0 = b0 ? *b0 : 0.f;
+  const float biasv = (DUAL && b0v) ? *b0v : 0.f;
   // 8 lanes per pixel, each a 16-byte slice of every 128-byte channel segment: a wave's load
   // instruction reads 8 pixels x 128 contiguous bytes (one lane per pixel read 384-byte rows in
   // 16-byte steps, one dependent load after another: 18 us for B = 256), then a 3-step
@@ -64,16 +72,26 @@ __device__ __forceinline__ HeadSoftmax head_logits_softmax(
       const int p = p0 < S2 ? p0 : S2 - 1;
       const int i = p / S, j = p - (p / S) * S;
       const bf16* row = H + ((size_t)(b * WP + i + 1) * WP + j + 1) * KP;
-      float acc = 0.f;
+      float acc = 0.f, acv = 0.f;
 #pragma unroll 4
       for (int c = sub * 8; c < KP; c += 64) {
         const bf16x8 v = *reinterpret_cast<const bf16x8*>(row + c);
 #pragma unroll
         for (int t = 0; t < 8; ++t) acc += (float)v[t] * ws[c + t];
+        if constexpr (DUAL) {
+#pragma unroll
+          for (int t = 0; t < 8; ++t) acv += (float)v[t] * ws[KP + c + t];
+        }
       }
       acc += __shfl_xor(acc, 1);
       acc += __shfl_xor(acc, 2);
       acc += __shfl_xor(acc, 4);
+      if constexpr (DUAL) {
+        acv += __shfl_xor(acv, 1);
+        acv += __shfl_xor(acv, 2);
+        acv += __shfl_xor(acv, 4);
+        if (sub == 0 && p0 < S2) zv[(size_t)b * S2 + p] = acv + biasv;
+      }
       if (sub == 0 && p0 < S2) z[p] = acc + bias0 + (pbias ? pbias[p] : 0.f);
     }
   }
@@ -106,6 +124,7 @@ __device__ __forceinline__ HeadSoftmax head_logits_softmax(
   return {gmax, 1.f / sum, mx, amax};
 }
 
+template <bool DUAL = false>
 __global__ void __launch_bounds__(kHeadFwdThreads)
 policy_head_fwd_kernel(const bf16* __restrict__ H, const float* __restrict__ w, const float* b0,
                        const float* __restrict__ pbias, float* __restrict__ probs,
@@ -114,17 +133,19 @@ policy_head_fwd_kernel(const bf16* __restrict__ H, const float* __restrict__ w, 
                        const float* __restrict__ pass_w, const float* __restrict__ pass_b,
                        float* __restrict__ zout, float* __restrict__ dpass,
                        float* __restrict__ acc, int S, int KP, int K, int mode, float gscale,
-                       float* __restrict__ dzsum = nullptr) {
+                       float* __restrict__ dzsum = nullptr,
+                       const float* __restrict__ wv = nullptr, const float* b0v = nullptr,
+                       float* __restrict__ zv = nullptr) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* z = smem;                        // S*S logits (+ the pass logit)
-  float* ws = smem + ((S * S + 4) & ~3);  // KP weights
+  float* ws = smem + ((S * S + 4) & ~3);  // KP weights (DUAL: 2 KP, the second head's behind)
   __shared__ float red[16];
   const int b = blockIdx.x;
   const int S2 = S * S;
   const bool has_pass = pass_w != nullptr;
   const int C = S2 + (has_pass ? 1 : 0);
-  const HeadSoftmax sm = head_logits_softmax(H, w, b0, pbias, pass_w, pass_b, zout, z, ws, red, S,
-                                             KP, K);
+  const HeadSoftmax sm = head_logits_softmax<DUAL>(H, w, b0, pbias, pass_w, pass_b, zout, z, ws,
+                                                   red, S, KP, K, wv, b0v, zv);
   const float gmax = sm.gmax, inv = sm.inv, mx = sm.mx;
   const int amax = sm.amax;
   const int64_t lab = (mode && labels) ? labels[b] : -1;
@@ -201,6 +222,7 @@ policy_head_fwd_kernel(const bf16* __restrict__ H, const float* __restrict__ w, 
 // the label kernel's mode 1. hit = the lowest argmax of z is the lowest argmax of t.
 // One class per thread (C <= blockDim.x): the thread's target, probability and mask stay in
 // registers; one fused block reduction gives Tm, the loss and both argmaxes.
+template <bool DUAL = false>
 __global__ void __launch_bounds__(kHeadFwdThreads)
 policy_head_soft_kernel(const bf16* __restrict__ H, const float* __restrict__ w, const float* b0,
                         const float* __restrict__ pbias, float* __restrict__ probs,
@@ -208,10 +230,12 @@ policy_head_soft_kernel(const bf16* __restrict__ H, const float* __restrict__ w,
                         float* __restrict__ loss, float* __restrict__ dz, float* __restrict__ hit,
                         const float* __restrict__ pass_w, const float* __restrict__ pass_b,
                         float* __restrict__ zout, float* __restrict__ dpass, int S, int KP, int K,
-                        float gscale, float* __restrict__ dzsum) {
+                        float gscale, float* __restrict__ dzsum,
+                        const float* __restrict__ w2 = nullptr, const float* b02 = nullptr,
+                        float* __restrict__ z2 = nullptr) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* z = smem;                        // S*S logits (+ the pass logit)
-  float* ws = smem + ((S * S + 4) & ~3);  // KP weights
+  float* ws = smem + ((S * S + 4) & ~3);  // KP weights (DUAL: 2 KP, the second head's behind)
   __shared__ float red[5 * 16];           // per wave: Tm, loss, max t, its index, the z candidate
   const int b = blockIdx.x;
   const int S2 = S * S;
@@ -223,8 +247,8 @@ policy_head_soft_kernel(const bf16* __restrict__ H, const float* __restrict__ w,
   const bool live = p < C;
   const float t = live ? targets[(size_t)b * C + p] : 0.f;
   const float tpass = has_pass ? targets[(size_t)b * C + S2] : 0.f;  // block-uniform
-  const HeadSoftmax sm = head_logits_softmax(H, w, b0, pbias, pass_w, pass_b, zout, z, ws, red, S,
-                                             KP, K);
+  const HeadSoftmax sm = head_logits_softmax<DUAL>(H, w, b0, pbias, pass_w, pass_b, zout, z, ws,
+                                                   red, S, KP, K, w2, b02, z2);
   const float pr = live ? __expf(z[p] - sm.gmax) * sm.inv : 0.f;
   const float m = (pr >= 1e-7f && pr <= 1.f - 1e-7f) ? 1.f : 0.f;
   const float sw = sweight ? sweight[b] : 1.f;
@@ -385,17 +409,127 @@ head_bwd_kernel(const bf16* __restrict__ H, const float* __restrict__ w,
   }
 }
 
+// head_bwd_kernel for two 1x1 heads on one trunk output (the policy-value network): H is read
+// once, dH[b,p,k] = (dzp[b,p] wp[k] + dzv[b,p] wv[k]) (H[b,p,k] > 0) is written once, and the
+// block's partials of both weight gradients go to dwpart[blk][0][k] = sum_p dzp H[., k] and
+// dwpart[blk][1][k] = sum_p dzv H[., k] (rows of 2 KP floats).
+template <int CH>
+__global__ void __launch_bounds__(kHeadThreads)
+head_bwd2_kernel(const bf16* __restrict__ H, const float* __restrict__ wp,
+                 const float* __restrict__ wv, const float* __restrict__ dzp,
+                 const float* __restrict__ dzv, bf16* __restrict__ dH,
+                 float* __restrict__ dwpart, int npix, int pix_per_block, int S, int K,
+                 int relu_mask) {
+  constexpr int KP = CH * 8;
+  constexpr int PPI = kHeadThreads / CH;  // pixels per block iteration
+  __shared__ float ws[2][KP];
+  __shared__ __attribute__((aligned(16))) float dwl[2][PPI][KP];
+  for (int k = threadIdx.x; k < KP; k += blockDim.x) {
+    ws[0][k] = k < K ? wp[k] : 0.f;
+    ws[1][k] = k < K ? wv[k] : 0.f;
+  }
+  __syncthreads();
+  const int S2 = S * S, WP = S + 2;
+  const int ch = threadIdx.x % CH, sub = threadIdx.x / CH;
+  float wl[8], vl[8], dwa[8], dva[8];
+#pragma unroll
+  for (int t = 0; t < 8; ++t) {
+    wl[t] = ws[0][ch * 8 + t];
+    vl[t] = ws[1][ch * 8 + t];
+    dwa[t] = 0.f;
+    dva[t] = 0.f;
+  }
+  const int pbeg = blockIdx.x * pix_per_block;
+  const int pend = min(npix, pbeg + pix_per_block);
+  if (sub < PPI) {
+    // 8 pixels per batch: all loads issued before any use (memory-level parallelism)
+    constexpr int U = 8;
+    for (int P0 = pbeg + sub; P0 < pend; P0 += U * PPI) {
+      size_t off[U];
+      float g[U], gv[U];
+      bf16x8 hv[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int P = min(P0 + u * PPI, pend - 1);
+        const int b = P / S2, p = P - (P / S2) * S2;
+        const int i = p / S, j = p - (p / S) * S;
+        off[u] = ((size_t)(b * WP + i + 1) * WP + j + 1) * KP + ch * 8;
+        const bool in = P0 + u * PPI < pend;
+        g[u] = in ? dzp[P] : 0.f;
+        gv[u] = in ? dzv[P] : 0.f;
+        hv[u] = *reinterpret_cast<const bf16x8*>(H + off[u]);
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        bf16x8 o;
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+          const float hf = (float)hv[u][t];
+          float d = g[u] * wl[t] + gv[u] * vl[t];
+          if (relu_mask && !(hf > 0.f)) d = 0.f;
+          o[t] = (bf16)d;
+          dwa[t] += g[u] * hf;
+          dva[t] += gv[u] * hf;
+        }
+        if (dH && P0 + u * PPI < pend) *reinterpret_cast<bf16x8*>(dH + off[u]) = o;
+      }
+    }
+    float4* dst = reinterpret_cast<float4*>(&dwl[0][sub][ch * 8]);
+    dst[0] = make_float4(dwa[0], dwa[1], dwa[2], dwa[3]);
+    dst[1] = make_float4(dwa[4], dwa[5], dwa[6], dwa[7]);
+    dst = reinterpret_cast<float4*>(&dwl[1][sub][ch * 8]);
+    dst[0] = make_float4(dva[0], dva[1], dva[2], dva[3]);
+    dst[1] = make_float4(dva[4], dva[5], dva[6], dva[7]);
+  }
+  __syncthreads();
+  for (int k = threadIdx.x; k < 2 * KP; k += blockDim.x) {
+    const int hd = k / KP, kk = k - hd * KP;
+    float v = 0.f;
+#pragma unroll
+    for (int r = 0; r < PPI; ++r) v += dwl[hd][r][kk];
+    dwpart[(size_t)blockIdx.x * 2 * KP + k] = v;
+  }
+}
+
+// This thread's share of the sum of n floats (fixed order): 16-byte loads, four in flight per
+// thread on independent sums (one dependent 4-byte load at a time took 24 us for 256 x 361
+// values -- the whole value-net step's longest small kernel); scalar loads when dz is not
+// 16-byte aligned.
+__device__ __forceinline__ float sum_all_share(const float* __restrict__ dz, size_t n) {
+  const size_t n4 = (reinterpret_cast<uintptr_t>(dz) & 15) ? 0 : n / 4;
+  const float4* d4 = reinterpret_cast<const float4*>(dz);
+  const size_t bt = blockDim.x;
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+  size_t i = threadIdx.x;
+  for (; i + 3 * bt < n4; i += 4 * bt) {
+    const float4 a = d4[i], b = d4[i + bt], c = d4[i + 2 * bt], e = d4[i + 3 * bt];
+    s0 += (a.x + a.y) + (a.z + a.w);
+    s1 += (b.x + b.y) + (b.z + b.w);
+    s2 += (c.x + c.y) + (c.z + c.w);
+    s3 += (e.x + e.y) + (e.z + e.w);
+  }
+  for (; i < n4; i += bt) {
+    const float4 a = d4[i];
+    s0 += (a.x + a.y) + (a.z + a.w);
+  }
+  for (size_t j = n4 * 4 + threadIdx.x; j < n; j += bt) s1 += dz[j];
+  return (s0 + s1) + (s2 + s3);
+}
+
 // Column sums of a row-major [rows][ld] fp32 matrix over 64-column tiles: 1024 threads = 64
 // columns x 16 row lanes (each row segment is one coalesced 256-byte read), 16-way LDS combine.
 // Blocks [0, ceil(K/64)): dw[k] = sum_blk dwpart[blk][k]; the rest: dpbias[p] = sum_b dz[b][p]
 // and db0 += the block's sum of its dpbias columns.
+template <bool DUAL = false>
 __global__ void __launch_bounds__(1024)
 head_bwd_reduce_kernel(const float* __restrict__ dwpart, const float* __restrict__ dz,
                        float* __restrict__ dw, float* __restrict__ db0,
                        float* __restrict__ dpbias, int nblk, int B, int S2, int KP, int K,
                        const float* __restrict__ mloss = nullptr,
                        const float* __restrict__ mhit = nullptr, float* __restrict__ acc = nullptr,
-                       const float* __restrict__ dzsum = nullptr) {
+                       const float* __restrict__ dzsum = nullptr,
+                       const float* __restrict__ dzv = nullptr, float* __restrict__ dwv = nullptr,
+                       float* __restrict__ db0v = nullptr) {
   __shared__ float red[16][65];
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
   const int kt = (K + 63) / 64;
@@ -403,33 +537,14 @@ head_bwd_reduce_kernel(const float* __restrict__ dwpart, const float* __restrict
     // the last block: db0 = sum of all dz (fixed summation order, so the step is bit-for-bit
     // reproducible -- per-block atomics made it depend on block timing), and the forward's
     // running metrics acc[0] += sum loss, acc[1] += sum hit (instead of two contended device
-    // atomics per board in the head forward)
-    float d = 0.f, a = 0.f, h = 0.f;
+    // atomics per board in the head forward); DUAL: db0v = sum of all dzv as well
+    float d = 0.f, a = 0.f, h = 0.f, e = 0.f;
     if (db0 && dzsum) {  // the head forward's per-board sums
       for (int i = threadIdx.x; i < B; i += blockDim.x) d += dzsum[i];
     } else if (db0) {
-      // all of dz (the value head: no per-board sums): 16-byte loads, four in flight per
-      // thread on independent sums (one dependent 4-byte load at a time took 24 us for
-      // 256 x 361 values -- the whole value-net step's longest small kernel)
-      const size_t n = (size_t)B * S2, n4 = (reinterpret_cast<uintptr_t>(dz) & 15) ? 0 : n / 4;
-      const float4* d4 = reinterpret_cast<const float4*>(dz);
-      const size_t bt = blockDim.x;
-      float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-      size_t i = threadIdx.x;
-      for (; i + 3 * bt < n4; i += 4 * bt) {
-        const float4 a = d4[i], b = d4[i + bt], c = d4[i + 2 * bt], e = d4[i + 3 * bt];
-        s0 += (a.x + a.y) + (a.z + a.w);
-        s1 += (b.x + b.y) + (b.z + b.w);
-        s2 += (c.x + c.y) + (c.z + c.w);
-        s3 += (e.x + e.y) + (e.z + e.w);
-      }
-      for (; i < n4; i += bt) {
-        const float4 a = d4[i];
-        s0 += (a.x + a.y) + (a.z + a.w);
-      }
-      for (size_t j = n4 * 4 + threadIdx.x; j < n; j += bt) s1 += dz[j];
-      d = (s0 + s1) + (s2 + s3);
+      d = sum_all_share(dz, (size_t)B * S2);  // the value head: no per-board sums
     }
+    if constexpr (DUAL) e = sum_all_share(dzv, (size_t)B * S2);
     if (acc)
       for (int i = threadIdx.x; i < B; i += blockDim.x) {
         a += mloss[i];
@@ -438,20 +553,24 @@ head_bwd_reduce_kernel(const float* __restrict__ dwpart, const float* __restrict
     d = warp_sum(d);
     a = warp_sum(a);
     h = warp_sum(h);
+    if constexpr (DUAL) e = warp_sum(e);
     if (tx == 0) {
       red[ty][0] = d;
       red[ty][1] = a;
       red[ty][2] = h;
+      if constexpr (DUAL) red[ty][3] = e;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-      float sd = 0.f, sa = 0.f, sh = 0.f;
+      float sd = 0.f, sa = 0.f, sh = 0.f, se = 0.f;
       for (int k = 0; k < (int)(blockDim.x >> 6); ++k) {
         sd += red[k][0];
         sa += red[k][1];
         sh += red[k][2];
+        if constexpr (DUAL) se += red[k][3];
       }
       if (db0) *db0 = sd;
+      if constexpr (DUAL) *db0v = se;
       if (acc) {
         acc[0] += sa;
         acc[1] += sh;
@@ -459,12 +578,15 @@ head_bwd_reduce_kernel(const float* __restrict__ dwpart, const float* __restrict
     }
     return;
   }
-  const bool isw = (int)blockIdx.x < kt;
-  const int col = (isw ? (int)blockIdx.x : (int)blockIdx.x - kt) * 64 + tx;
+  // DUAL: dwpart rows are [2][KP]; blocks [kt, 2 kt) sum the second head's half into dwv
+  const int nwb = DUAL ? 2 * kt : kt;
+  const bool isw = (int)blockIdx.x < nwb;
+  const bool second = DUAL && isw && (int)blockIdx.x >= kt;
+  const int col = ((int)blockIdx.x - (isw ? (second ? kt : 0) : nwb)) * 64 + tx;
   const int ncol = isw ? K : S2;
   const int rows = isw ? nblk : B;
-  const int ld = isw ? KP : S2;
-  const float* src = isw ? dwpart : dz;
+  const int ld = isw ? (DUAL ? 2 * KP : KP) : S2;
+  const float* src = isw ? (second ? dwpart + KP : dwpart) : dz;
   float s = 0.f;
   if (col < ncol) {
     constexpr int U = 4;
@@ -486,7 +608,7 @@ head_bwd_reduce_kernel(const float* __restrict__ dwpart, const float* __restrict
     for (int r = 0; r < 16; ++r) v += red[r][tx];
     if (col < ncol) {
       if (isw) {
-        dw[col] = v;
+        (second ? dwv : dw)[col] = v;
       } else if (dpbias) {
         dpbias[col] = v;
       }
@@ -695,10 +817,9 @@ RAG_API int rag_policy_head_fwd(const void* H, const float* w, const float* b0,
                                 float gscale, hipStream_t stream) {
   if (pass_w && !pass_b) return -1;
   const size_t sm = (size_t)(((S * S + 4) & ~3) + KP) * sizeof(float);
-  policy_head_fwd_kernel<<<B, kHeadFwdThreads, sm, stream>>>((const bf16*)H, w, b0, pbias, probs,
-                                                          labels, sweight, loss, dz, hit, pass_w,
-                                                          pass_b, zout, dpass, acc, S, KP, K,
-                                                          mode, gscale, dzsum);
+  policy_head_fwd_kernel<false><<<B, kHeadFwdThreads, sm, stream>>>(
+      (const bf16*)H, w, b0, pbias, probs, labels, sweight, loss, dz, hit, pass_w, pass_b, zout,
+      dpass, acc, S, KP, K, mode, gscale, dzsum);
   return (int)hipGetLastError();
 }
 
@@ -716,9 +837,37 @@ RAG_API int rag_policy_head_soft(const void* H, const float* w, const float* b0,
   if (!targets || B <= 0 || S <= 0) return -1;
   if (S * S + (pass_w ? 1 : 0) > kHeadFwdThreads) return -1;  // one class per thread
   const size_t sm = (size_t)(((S * S + 4) & ~3) + KP) * sizeof(float);
-  policy_head_soft_kernel<<<B, kHeadFwdThreads, sm, stream>>>(
+  policy_head_soft_kernel<false><<<B, kHeadFwdThreads, sm, stream>>>(
       (const bf16*)H, w, b0, pbias, probs, targets, sweight, loss, dz, hit, pass_w, pass_b, zout,
       dpass, S, KP, K, gscale, dzsum);
+  return (int)hipGetLastError();
+}
+
+// Both heads of the policy-value network in one pass over the trunk's last activation: the
+// policy head of rag_policy_head_fwd (labels, modes 0 / 1 / 2) or, with dense `targets`, of
+// rag_policy_head_soft (categorical cross-entropy), without a pass logit and without in-kernel
+// metrics, plus the value head's 1x1 conv zv [B, S*S] = H . wv + b0v from the same loaded
+// channels. labels and targets exclude each other; targets need mode 1.
+RAG_API int rag_policy_head_dual(const void* H, const float* w, const float* b0,
+                                 const float* pbias, const float* wv, const float* b0v,
+                                 float* probs, float* zv, const int64_t* labels,
+                                 const float* targets, const float* sweight, float* loss,
+                                 float* dz, float* hit, float* dzsum, int B, int S, int KP, int K,
+                                 int mode, float gscale, hipStream_t stream) {
+  if (!H || !w || !wv || !zv || !probs || B <= 0 || S <= 0 || K <= 0 || K > KP || KP % 8)
+    return -1;
+  if (targets && (labels || mode != 1)) return -1;
+  if (S * S > kHeadFwdThreads) return -1;  // the soft form's one class per thread
+  const size_t sm = (size_t)(((S * S + 4) & ~3) + 2 * KP) * sizeof(float);
+  if (sm > 64 * 1024) return -1;
+  if (targets)
+    policy_head_soft_kernel<true><<<B, kHeadFwdThreads, sm, stream>>>(
+        (const bf16*)H, w, b0, pbias, probs, targets, sweight, loss, dz, hit, nullptr, nullptr,
+        nullptr, nullptr, S, KP, K, gscale, dzsum, wv, b0v, zv);
+  else
+    policy_head_fwd_kernel<true><<<B, kHeadFwdThreads, sm, stream>>>(
+        (const bf16*)H, w, b0, pbias, probs, labels, sweight, loss, dz, hit, nullptr, nullptr,
+        nullptr, nullptr, nullptr, S, KP, K, mode, gscale, dzsum, wv, b0v, zv);
   return (int)hipGetLastError();
 }
 
@@ -747,7 +896,7 @@ RAG_API int rag_head_bwd(const void* H, const float* w, const float* dz, void* d
   }
 #undef RAG_HB
   const int rblocks = (K + 63) / 64 + (S * S + 63) / 64;
-  head_bwd_reduce_kernel<<<rblocks + 1, 1024, 0, stream>>>(
+  head_bwd_reduce_kernel<false><<<rblocks + 1, 1024, 0, stream>>>(
       work, dz, dw, db0, dpbias, nblk, B, S * S, KP, K, mloss, mhit, acc, dzsum);
   return (int)hipGetLastError();
 }
@@ -757,6 +906,44 @@ RAG_API size_t rag_head_bwd_workspace(int B, int S, int KP) {
   int nblk = (npix + 47) / 48;
   if (nblk > kHeadBwdBlocks) nblk = kHeadBwdBlocks;
   return (size_t)nblk * KP;
+}
+
+// Backward of two 1x1 heads on one trunk output (policy wp / dzp, value wv / dzv; all outputs
+// overwritten): dH = (dzp wp + dzv wv) (H > 0 or no mask) written once, dwp, dwv, dpbias =
+// sum_b dzp, db0p = sum dzsum (or sum dzp), db0v = sum dzv; mloss / mhit / acc as rag_head_bwd.
+// work: >= rag_head_bwd2_workspace(B, S, KP) floats. dH and dpbias are optional.
+RAG_API int rag_head_bwd2(const void* H, const float* wp, const float* wv, const float* dzp,
+                          const float* dzv, void* dH, float* dwp, float* dwv, float* db0p,
+                          float* db0v, float* dpbias, float* work, int B, int S, int KP, int K,
+                          int relu_mask, const float* mloss, const float* mhit, float* acc,
+                          const float* dzsum, hipStream_t stream) {
+  if (!H || !wp || !wv || !dzp || !dzv || !dwp || !dwv || !db0p || !db0v || !work) return -1;
+  if (B <= 0 || S <= 0 || K <= 0 || K > KP) return -1;
+  if (acc && (!mloss || !mhit)) return -1;
+  const int npix = B * S * S;
+  int nblk = (npix + 47) / 48;
+  if (nblk > kHeadBwdBlocks) nblk = kHeadBwdBlocks;
+  const int ppb = (npix + nblk - 1) / nblk;
+#define RAG_HB2(C)                                                                            \
+  case C:                                                                                     \
+    head_bwd2_kernel<C><<<nblk, kHeadThreads, 0, stream>>>((const bf16*)H, wp, wv, dzp, dzv,  \
+                                                           (bf16*)dH, work, npix, ppb, S, K,  \
+                                                           relu_mask);                        \
+    break;
+  switch (KP % 8 ? 0 : KP / 8) {
+    RAG_HB2(4) RAG_HB2(8) RAG_HB2(12) RAG_HB2(16) RAG_HB2(24) RAG_HB2(32) RAG_HB2(48) RAG_HB2(64)
+    default: return -1;
+  }
+#undef RAG_HB2
+  const int rblocks = 2 * ((K + 63) / 64) + (S * S + 63) / 64;
+  head_bwd_reduce_kernel<true><<<rblocks + 1, 1024, 0, stream>>>(
+      work, dzp, dwp, db0p, dpbias, nblk, B, S * S, KP, K, mloss, mhit, acc, dzsum, dzv, dwv,
+      db0v);
+  return (int)hipGetLastError();
+}
+
+RAG_API size_t rag_head_bwd2_workspace(int B, int S, int KP) {
+  return 2 * rag_head_bwd_workspace(B, S, KP);
 }
 
 RAG_API int rag_head_linear(const void* H, const float* w, const float* b0, float* z, int B,

@@ -467,7 +467,9 @@ def main(argv=None):
     ap.add_argument("--name", default="RocAlphaGo-MI355X")
     ap.add_argument("--dtype", choices=["bf16", "fp32"], default="bf16",
                     help="GPU compute precision of the networks (bf16 = fused HIP kernels)")
-    ap.add_argument("--value", default=None, help="value network JSON (mcts player)")
+    ap.add_argument("--value", default=None,
+                    help="value network JSON (mcts player; omit it with a CNNPolicyValue model, "
+                         "whose own value head is searched with)")
     ap.add_argument("--value-weights", default=None)
     ap.add_argument("--lmbda", type=float, default=None,
                     help="value/rollout mix (default 0.5 with a value net, else 1 = rollouts)")
@@ -502,7 +504,12 @@ def main(argv=None):
                 value = NeuralNetBase.load_model(args.value).set_dtype(args.dtype)
                 if args.value_weights:
                     value.model.load_weights(args.value_weights)
-            lmbda = args.lmbda if args.lmbda is not None else (0.5 if value is not None else 1.0)
+            from ..search.apv import is_dual
+            if is_dual(policy) and value is not None:
+                raise ValueError("%s is a policy-value network: it is searched with its own "
+                                 "value head, omit --value" % args.model)
+            has_value = value is not None or is_dual(policy)
+            lmbda = args.lmbda if args.lmbda is not None else (0.5 if has_value else 1.0)
             player = ParallelMCTSPlayer(policy, value, lmbda=lmbda, c_puct=args.c_puct,
                                         n_playout=args.playouts, batch=args.leaf_batch,
                                         virtual_loss=args.virtual_loss,

@@ -15,7 +15,9 @@ preallocated padded channels-last bf16 activations (layout: csrc/hip/conv.hip), 
 Heads: ``PolicyHeadEngine`` (1x1 conv -> per-position Bias -> softmax, with the cross-entropy /
 REINFORCE loss fused into the same kernel) and ``ValueHeadEngine`` (1x1 conv on HIP, then the two
 dense layers + tanh in csrc/hip/head.hip ``value_mlp_*`` for inference and csrc/hip/value_bwd.hip
-for training: forward, MSE tail and all head gradients in two launches, no library GEMMs).
+for training: forward, MSE tail and all head gradients in two launches, no library GEMMs), and
+``DualHeadEngine`` (the policy-value network: both heads on one trunk output, one forward launch
+and one backward that writes the trunk-top gradient of both heads once).
 
 No autograd graph is built on the hot path; ``models/kerasish.py`` exposes these engines through
 torch.autograd.Function wrappers for generic use and calls ``train_step`` directly for speed.
@@ -855,3 +857,70 @@ class ValueHeadEngine(object):
         h = self.trunk.output(B)
         ops.head_bwd(h, w, dz.contiguous(), self.trunk.top_grad(B), dw, db0, None, self.K,
                      relu_mask=self.trunk.top_relu)
+
+
+class DualHeadEngine(object):
+    """Both heads of the policy-value network on one trunk output: the policy head (1x1 conv ->
+    per-position Bias -> softmax, loss fused) and the value head's 1x1 conv in ONE forward
+    launch (ops.policy_head_dual), and one backward (ops.head_bwd2) that writes the trunk-top
+    gradient dH = mask (dz_p w_p + dz_v w_v) once. The value MLP runs on ``zv`` / into ``dzv``
+    (ops.value_mlp_fwd / value_mlp_train, called by fused.DualPlan)."""
+
+    def __init__(self, trunk, K):
+        self.trunk = trunk
+        self.K = K
+        self.S = trunk.S
+        self.gen = 0
+        self._B = 0
+        self._macc = None
+
+    def ensure(self, B):
+        if B <= self._B:
+            return
+        self.gen += 1  # buffers moved (captured graphs)
+        dev = self.trunk.device
+        S2 = self.S * self.S
+        self.probs = torch.empty((B, S2), device=dev)
+        self.dz = torch.empty((B, S2), device=dev)
+        self.loss = torch.empty((B,), device=dev)
+        self.hit = torch.empty((B,), device=dev)
+        self.dzsum = torch.empty((B,), device=dev)
+        self.zv = torch.empty((B, S2), device=dev)
+        self.dzv = torch.empty((B, S2), device=dev)
+        self._B = B
+
+    def forward(self, B, w, b0, pbias, wv, b0v, labels=None, sweight=None, mode=0, gscale=1.0,
+                acc=None, targets=None):
+        """(probs [B, S*S], zv [B, S*S]). labels / targets / mode / gscale / acc as
+        PolicyHeadEngine.forward: a training forward's metrics are added to ``acc`` by the
+        matching backward()."""
+        if mode and acc is not None and self._macc is not None:
+            raise RuntimeError("DualHeadEngine: training forward with acc= while the previous "
+                               "one's metrics are still pending (backward() not called)")
+        if not mode and acc is not None:
+            raise ValueError("DualHeadEngine: no in-kernel metrics in an inference forward")
+        if targets is not None and (labels is not None or mode != 1):
+            raise ValueError("DualHeadEngine: targets= excludes labels= and needs mode 1")
+        self.ensure(B)
+        self._macc = None
+        ops.policy_head_dual(self.trunk.output(B), w, b0, pbias, wv, b0v, self.probs[:B],
+                             self.zv[:B], self.K, labels=labels, targets=targets,
+                             sweight=sweight, loss=self.loss[:B] if mode else None,
+                             dz=self.dz[:B] if mode else None,
+                             hit=self.hit[:B] if mode else None, mode=mode, gscale=gscale,
+                             dzsum=self.dzsum[:B] if mode else None)
+        self._macc = acc if mode else None
+        return self.probs[:B], self.zv[:B]
+
+    def reset_metrics(self):
+        self._macc = None
+
+    def backward(self, B, w, wv, dw, dwv, db0, db0v, dpbias):
+        """dz [B, S*S] (the forward's) and dzv [B, S*S] (the value MLP's) -> both head convs'
+        gradients, the Bias gradient and the trunk top gradient (ReLU-masked) in grad buffer 0."""
+        acc, self._macc = self._macc, None
+        ops.head_bwd2(self.trunk.output(B), w, wv, self.dz[:B], self.dzv[:B],
+                      self.trunk.top_grad(B), dw, dwv, db0, db0v, dpbias, self.K,
+                      relu_mask=self.trunk.top_relu,
+                      metrics=(self.loss[:B], self.hit[:B], acc) if acc is not None else None,
+                      dzsum=self.dzsum[:B])

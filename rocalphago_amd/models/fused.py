@@ -9,6 +9,9 @@
   ResnetPlan:  (functional) Conv2D linear -> [n_skip x (BN -> ReLU -> Conv2D linear) + sum-merge]*
                -> ReLU -> Conv2D 1x1 -> Flatten -> Bias -> softmax
                                                        (ResnetPolicy, reference policy.py:196-244)
+  DualPlan:    (functional, two outputs) [Conv2D 'same' + ReLU]* -> the PolicyPlan head (no pass
+               logit, output 0) and the ValuePlan head (output 1) on the same trunk output
+                                                       (CNNPolicyValue, models/policy_value.py)
 
 and executes them on the HIP engine (models/engine.py): one packed-input kernel (uint8 or fp32
 planes, optional gather + dihedral transform), one MFMA conv launch per layer, the fused head
@@ -18,7 +21,8 @@ into the model's flat fp32 gradient buffer (ready for one all-reduce and the fus
 import torch
 
 from ..ops import hipops as ops
-from .engine import BNSpec, ConvSpec, HipTrunk, PolicyHeadEngine, ResTrunk, ValueHeadEngine
+from .engine import (BNSpec, ConvSpec, DualHeadEngine, HipTrunk, PolicyHeadEngine, ResTrunk,
+                     ValueHeadEngine)
 
 
 def _conv_ok(ld):
@@ -31,6 +35,8 @@ def _conv_ok(ld):
 
 def detect_plan(model):
     if model.functional:
+        if len(model.net.output_names) > 1:
+            return _detect_dual(model)
         return _detect_resnet(model)
     L = model.layers
     n = 0
@@ -138,14 +144,14 @@ class _TrunkPlan(object):
                        index=index, transforms=transforms, nplanes=self.trunk.specs[0].cin)
         return B
 
-    def head_params(self):
-        p = self.net.params_of(self.head_name)
+    def head_params(self, name=None):
+        p = self.net.params_of(name or self.head_name)
         w = p[0].reshape(-1)
         b0 = p[1] if len(p) > 1 else None
         return w, b0
 
-    def head_grads(self):
-        g = self.net.grads_of(self.head_name)
+    def head_grads(self, name=None):
+        g = self.net.grads_of(name or self.head_name)
         return g[0].reshape(-1), (g[1] if len(g) > 1 else torch.zeros(1, device=self.net.device))
 
     def layer_offsets(self):
@@ -283,6 +289,152 @@ class ValuePlan(_TrunkPlan):
                                     dz=dz).sum()
         dw, db0 = self.head_grads()
         self.head.backward_conv(B, w, dz, dw, db0)
+        dWs, dbs = self._grads()
+        self.trunk.backward(B, dWs, dbs, on_layer_done=on_layer_grads)
+        return lossv.detach()
+
+
+def _detect_dual(model):
+    """Match CNNPolicyValue's functional graph exactly (models/policy_value.py: the layer list in
+    its order, every layer fed by the one the graph names); anything else runs the generic
+    executor."""
+    L = model.layers
+    S = model.input_shape[-1] if model.input_shape else None
+    if not S or S > 25 or model.input_shape[-2] != S or L[0].class_name != "InputLayer":
+        return None
+    n = 1
+    while n < len(L) and L[n].class_name == "Convolution2D" and L[n].inbound == [L[n - 1].name] \
+            and _conv_ok(L[n]) and L[n].config.get("activation") == "relu":
+        n += 1
+    convs, rest = L[1:n], L[n:]
+    if not convs or convs[-1].config["nb_row"] > 3 or len(rest) != 8:
+        return None
+    top = convs[-1].name
+
+    def head_conv(ld):
+        c = ld.config
+        return (ld.class_name == "Convolution2D" and ld.inbound == [top] and _conv_ok(ld) and
+                c["nb_filter"] == 1 and c["nb_row"] == 1 and
+                c.get("activation", "linear") == "linear")
+
+    def chain(lds, classes):
+        return all(ld.class_name == c and ld.inbound == [prev.name]
+                   for ld, prev, c in zip(lds[1:], lds, classes))
+
+    pol, val = rest[:4], rest[4:]
+    if not head_conv(pol[0]) or not chain(pol, ["Flatten", "Bias", "Activation"]) or \
+            pol[3].config["activation"] != "softmax":
+        return None
+    if not head_conv(val[0]) or not chain(val, ["Flatten", "Dense", "Dense"]) or \
+            val[3].config["output_dim"] != 1 or val[3].config.get("activation") != "tanh" or \
+            val[2].config.get("activation", "linear") not in ops.MLP_ACTS or \
+            not all(ld.config.get("bias", True) for ld in val[2:]):
+        return None
+    if list(model.net.output_names) != [pol[3].name, val[3].name]:
+        return None
+    return DualPlan(model, convs, pol[0], pol[2], val[0], val[2], val[3])
+
+
+class DualPlan(_TrunkPlan):
+    """CNNPolicyValue on the HIP engine: one trunk, both heads in one forward launch
+    (DualHeadEngine), the value MLP on ops.value_mlp_fwd / value_mlp_train, and one head
+    backward that writes the trunk-top gradient of both heads once (ops.head_bwd2)."""
+
+    multi_output = True
+    pass_name = None
+    loss_mode = staticmethod(PolicyPlan.loss_mode)
+
+    def __init__(self, model, convs, head_conv, bias_layer, vhead_conv, dense1, dense2):
+        super(DualPlan, self).__init__(model, convs, head_conv)
+        self.bias_name = bias_layer.name
+        self.vhead_name = vhead_conv.name
+        self.d1, self.d2 = dense1.name, dense2.name
+        self.act1 = dense1.config.get("activation", "linear")
+        self.head = DualHeadEngine(self.trunk, self.K)
+        self._vw = None
+
+    def _pass_params(self):
+        return None
+
+    def _dense_params(self):
+        return self.net.params_of(self.d1) + self.net.params_of(self.d2)
+
+    def _heads(self, B, **kw):
+        w, b0 = self.head_params()
+        wv, b0v = self.head_params(self.vhead_name)
+        pb = self.net.params_of(self.bias_name)[0]
+        return self.head.forward(B, w, b0, pb, wv, b0v, **kw)
+
+    def forward(self, x, index=None, transforms=None, clone=True):
+        """(move probabilities [B, S*S], values [B]) from one trunk pass. clone=False returns
+        the head's own probability buffer (valid until the next forward of this plan)."""
+        B = self.prepare(x, index, transforms)
+        self.trunk.forward(B)
+        probs, zv = self._heads(B)
+        W1, b1, W2, b2 = self._dense_params()
+        v = ops.value_mlp_fwd(zv, W1, b1, W2, b2, act=self.act1).reshape(-1)
+        return (probs.clone() if clone else probs), v
+
+    def _value_weights(self, B, value_weight):
+        if self._vw is None or self._vw[0] != value_weight or self._vw[1].numel() < B:
+            self._vw = (value_weight, torch.full((B,), float(value_weight),
+                                                 device=self.net.device))
+        return self._vw[1][:B]
+
+    def train_step(self, x, ys, losses, loss_weights=None, want_acc=False, index=None,
+                   transforms=None):
+        """One fused step on (Yp, Yv) under (categorical_crossentropy, mse): ([policy loss,
+        value loss], accuracy or None); None (nothing done) for any other pair of losses, for
+        dense policy targets under another policy loss, or a value weight <= 0."""
+        losses = list(losses)
+        if len(losses) != 2 or losses[0] != "categorical_crossentropy" or \
+                losses[1] not in ("mse", "mean_squared_error"):
+            return None
+        wp, wv = (1.0, 1.0) if loss_weights is None else loss_weights
+        if not wv > 0:
+            return None
+        yp, yv = ys
+        labels = targets = None
+        if bool(((yp.sum(1) == 1) & (yp.max(1).values == 1)).all()):
+            labels = yp.argmax(1)
+        else:
+            targets = yp.float().contiguous()
+        B = self.prepare(x, index, transforms)
+        lv = self.fwd_bwd(B, labels, None, 1, float(wp) / B, yv, float(wv), targets=targets)
+        lp = float(self.head.loss[:B].mean())
+        acc = float(self.head.hit[:B].mean()) if want_acc else None
+        return [lp, float(lv)], acc
+
+    def fwd_bwd(self, B, labels, sw, mode, gscale, y, value_weight, on_layer_grads=None,
+                metrics=None, targets=None):
+        """Forward, both losses and the full backward into net.flat_grad, no host syncs. The
+        policy side as PolicyPlan.fwd_bwd; y [B] (or [B, 1]): the value targets under
+        value_weight * mean((v - y)^2). Returns mean((v - y)^2) (unweighted) as a device
+        scalar."""
+        if not value_weight > 0:
+            raise ValueError("DualPlan.fwd_bwd: value_weight must be > 0, got %r"
+                             % (value_weight,))
+        self.trunk.forward(B, training=True)
+        _, zv = self._heads(B, labels=labels, sweight=sw, mode=mode, gscale=gscale, acc=metrics,
+                            targets=targets)
+        try:
+            W1, b1, W2, b2 = self._dense_params()
+            gW1, gb1, gW2, gb2 = self.net.grads_of(self.d1) + self.net.grads_of(self.d2)
+            yv = y.reshape(-1).float().contiguous()
+            # a constant sample weight: value_bwd.hip divides by the share of non-zero weights
+            # (1), so the value term is value_weight * mean((v - y)^2) and dzv is scaled
+            vw = self._value_weights(B, value_weight)
+            lossv = ops.value_mlp_train(zv, W1, b1, W2, b2, yv, vw, self.act1, gW1, gb1, gW2,
+                                        gb2, dz=self.head.dzv[:B]).sum() / value_weight
+            w, _ = self.head_params()
+            wv, _ = self.head_params(self.vhead_name)
+            dw, db0 = self.head_grads()
+            dwv, db0v = self.head_grads(self.vhead_name)
+            dpb = self.net.grads_of(self.bias_name)[0]
+            self.head.backward(B, w, wv, dw, dwv, db0, db0v, dpb)
+        except BaseException:
+            self.head.reset_metrics()  # a retrying caller's next forward must not raise
+            raise
         dWs, dbs = self._grads()
         self.trunk.backward(B, dWs, dbs, on_layer_done=on_layer_grads)
         return lossv.detach()

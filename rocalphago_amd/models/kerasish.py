@@ -472,6 +472,8 @@ class KerasNet(torch.nn.Module):
                 continue
             vals[ld.name] = self._run_layer(ld, [vals[n] for n in ld.inbound], by_layer[ld.name],
                                             training)
+        if len(self.output_names) > 1:
+            return [vals[n] for n in self.output_names]
         return vals[self.output_names[0]]
 
 
@@ -660,7 +662,13 @@ class Model(object):
         return self.net.input_shape
 
     @property
+    def n_outputs(self):
+        return len(self.net.output_names) if self.functional else 1
+
+    @property
     def output_shape(self):
+        if self.n_outputs > 1:
+            return [self.net.shapes[n] for n in self.net.output_names]
         last = self.net.output_names[0] if self.functional else self.layers[-1].name
         return self.net.shapes[last]
 
@@ -753,7 +761,23 @@ class Model(object):
         self.set_weights(weights)
 
     # ---- compile / train / predict
-    def compile(self, loss, optimizer, metrics=None, **kw):
+    def compile(self, loss, optimizer, metrics=None, loss_weights=None, **kw):
+        """A multi-output model takes one loss per output (a list, in output order) and
+        optional ``loss_weights`` (default all 1): total loss = sum_i loss_weights[i] loss_i."""
+        n = self.n_outputs
+        if n > 1:
+            if not isinstance(loss, (list, tuple)) or len(loss) != n:
+                raise ValueError("a model with %d outputs takes a list of %d losses" % (n, n))
+            loss = list(loss)
+            loss_weights = [1.0] * n if loss_weights is None else [float(w) for w in
+                                                                   loss_weights]
+            if len(loss_weights) != n:
+                raise ValueError("loss_weights: one weight per output (%d) expected" % n)
+        elif isinstance(loss, (list, tuple)):
+            if len(loss) != 1:
+                raise ValueError("a single-output model takes one loss")
+            loss = loss[0]
+        self.loss_weights = loss_weights if n > 1 else None
         self.loss = loss
         self.optimizer = optimizer if not isinstance(optimizer, str) else SGD()
         self.metrics = list(metrics or [])
@@ -762,6 +786,9 @@ class Model(object):
         if callable(self.loss):
             return self.loss
         return OBJECTIVES[self.loss]
+
+    def _loss_fns(self):
+        return [l if callable(l) else OBJECTIVES[l] for l in self.loss]
 
     def _plan_for(self):
         if not self._plan_checked:
@@ -787,6 +814,7 @@ class Model(object):
         n = len(X)
         bs = int(batch_size or 1024)
         outs = []
+        multi = self.n_outputs > 1
         with torch.no_grad():
             for s in range(0, max(n, 1), bs):
                 x = self._to_tensor(X[s:s + bs])
@@ -794,7 +822,13 @@ class Model(object):
                     out = plan.forward(x)
                 else:
                     out = self.net.forward(x.float(), training=False)
-                outs.append(out.detach().cpu())
+                if multi:
+                    outs.append([o.detach().cpu() for o in out])
+                else:
+                    outs.append(out.detach().cpu())
+        if multi:  # a list of arrays in output order (a fused plan's [B] values as [B, 1])
+            cols = [torch.cat(c) if len(c) > 1 else c[0] for c in zip(*outs)]
+            return [c.reshape(c.shape[0], -1).numpy() for c in cols]
         return torch.cat(outs).numpy() if len(outs) > 1 else outs[0].numpy()
 
     def predict_on_batch(self, X):
@@ -803,6 +837,8 @@ class Model(object):
     def train_on_batch(self, X, Y, sample_weight=None):
         if self.optimizer is None:
             raise RuntimeError("compile() the model before training")
+        if self.n_outputs > 1:
+            return self._train_on_batch_multi(X, Y, sample_weight)
         plan = self._plan_for()
         x = self._to_tensor(X)
         y = self._to_tensor(Y).float()
@@ -819,6 +855,56 @@ class Model(object):
         if self.metrics:
             return [loss, acc]
         return loss
+
+    def _targets_multi(self, Y):
+        n = self.n_outputs
+        if not isinstance(Y, (list, tuple)) or len(Y) != n:
+            raise ValueError("a model with %d outputs takes a list of %d target arrays" % (n, n))
+        if not isinstance(self.loss, list):
+            raise RuntimeError("compile() the model with one loss per output before training")
+        ys = [self._to_tensor(y).float() for y in Y]
+        return [y.reshape(y.shape[0], -1) for y in ys]
+
+    def _train_on_batch_multi(self, X, Y, sample_weight=None):
+        """[total, loss_0, .., loss_{n-1}] (+ the accuracy of output 0 with the "accuracy"
+        metric); total = sum_i loss_weights[i] loss_i."""
+        if sample_weight is not None:
+            raise NotImplementedError("sample_weight with a multi-output model")
+        ys = self._targets_multi(Y)
+        x = self._to_tensor(X)
+        want_acc = "accuracy" in self.metrics
+        plan = self._plan_for()
+        result = None
+        if plan is not None and getattr(plan, "multi_output", False):
+            result = plan.train_step(x, ys, self.loss, loss_weights=self.loss_weights,
+                                     want_acc=want_acc)
+        if result is None:
+            result = self._generic_train_step_multi(x, ys)
+        losses, acc = result
+        if self.grad_allreduce is not None:
+            self.grad_allreduce(self.net.flat_grad)
+        self.optimizer.apply(self.net)
+        total = sum(w * l for w, l in zip(self.loss_weights, losses))
+        return [total] + list(losses) + ([acc] if want_acc else [])
+
+    def _generic_train_step_multi(self, x, ys):
+        net = self.net
+        params = [v.detach().clone().requires_grad_() for v in net._views]
+        outs = net.forward(x.float(), training=True, params=params)
+        losses = [_objective(fn, y, o) for fn, y, o in zip(self._loss_fns(), ys, outs)]
+        total = sum(w * l for w, l in zip(self.loss_weights, losses))
+        grads = torch.autograd.grad(total, params, allow_unused=True)
+        with torch.no_grad():
+            for (_, wname, _), v, p in zip(net.weight_names, net._views, params):
+                if "_running_" in wname:
+                    v.copy_(p)
+            for gv, g in zip(net._gviews, grads):
+                if g is None:
+                    gv.zero_()
+                else:
+                    gv.copy_(g)
+        acc = _accuracy(ys[0], outs[0].detach()) if "accuracy" in self.metrics else None
+        return [float(l.detach()) for l in losses], acc
 
     def _generic_train_step(self, x, y, sw):
         net = self.net
@@ -843,6 +929,14 @@ class Model(object):
         return float(loss.detach()), acc
 
     def test_on_batch(self, X, Y):
+        if self.n_outputs > 1:
+            outs = [torch.from_numpy(o) for o in self.predict(X)]
+            ys = [y.cpu() for y in self._targets_multi(Y)]
+            losses = [float(_objective(fn, y, o))
+                      for fn, y, o in zip(self._loss_fns(), ys, outs)]
+            total = sum(w * l for w, l in zip(self.loss_weights, losses))
+            acc = [_accuracy(ys[0], outs[0])] if "accuracy" in self.metrics else []
+            return [total] + losses + acc
         out = torch.from_numpy(np.asarray(self.predict(X)))
         y = torch.as_tensor(np.asarray(Y), dtype=torch.float32)
         loss = float(_objective(self._loss_fn(), y, out))

@@ -49,6 +49,11 @@ class NeuralNetBase(object):
         name = spec.get('class', 'CNNPolicy')
         cls = NeuralNetBase.subclasses.get(name)
         if cls is None:
+            # the package's own networks register on import: a caller that imported only one
+            # of them can still load the others
+            from . import policy, policy_value, value  # noqa: F401
+            cls = NeuralNetBase.subclasses.get(name)
+        if cls is None:
             known = ", ".join(sorted(NeuralNetBase.subclasses))
             raise ValueError("%s names network class %r, which is not registered (known: %s); "
                              "decorate the class with @neuralnet" % (json_file, name, known))

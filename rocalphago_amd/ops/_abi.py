@@ -40,6 +40,9 @@ SIGNATURES = {
     "rag_policy_head_soft": [P] * 15 + [I, I, I, I, F, P],
     "rag_head_bwd": [P] * 8 + [I] * 5 + [P] * 5,
     "rag_head_bwd_workspace": [I, I, I],
+    "rag_policy_head_dual": [P] * 15 + [I, I, I, I, I, F, P],
+    "rag_head_bwd2": [P] * 12 + [I] * 5 + [P] * 5,
+    "rag_head_bwd2_workspace": [I, I, I],
     "rag_head_linear": [P, P, P, P, I, I, I, I, P],
     "rag_value_mlp_fwd": [P, P, P, P, P, P, P, P, I, I, I, I, P],
     "rag_value_mlp_workspace": [I, I],
@@ -78,6 +81,7 @@ SIGNATURES = {
 }
 
 RESTYPES = {"rag_conv_wgrad_workspace": SZ, "rag_head_bwd_workspace": SZ,
+            "rag_head_bwd2_workspace": SZ,
             "rag_ladder_workspace": SZ, "rag_wgrad_pending_bytes": SZ,
             "rag_value_mlp_workspace": SZ, "rag_value_mlp_bwd_workspace": SZ,
             "rag_rollout_park_bytes": C.c_long}

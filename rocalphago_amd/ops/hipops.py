@@ -539,6 +539,32 @@ def policy_head_soft(h, w, b0, pbias, probs, K, targets, sweight=None, loss=None
         _ptr(dzsum), B, S, KP, K, float(gscale), _stream()), "policy_head_soft")
 
 
+def policy_head_dual(h, w, b0, pbias, wv, b0v, probs, zv, K, labels=None, targets=None,
+                     sweight=None, loss=None, dz=None, hit=None, mode=0, gscale=1.0, dzsum=None):
+    """Both heads of the policy-value network in one pass over ``h``: policy_head_fwd
+    (``labels``, modes 0 / 1 / 2) or, with dense ``targets``, policy_head_soft (mode 1), without
+    a pass logit, plus the value head's 1x1 conv ``zv`` [B, S*S] = h . wv + b0v (fp32) from the
+    same loaded channels (head.hip, the DUAL forms of the two policy-head kernels)."""
+    B, WP, _, KP = h.shape
+    S = WP - 2
+    S2 = S * S
+    if targets is not None:
+        if labels is not None or mode != 1:
+            raise ValueError("policy_head_dual: targets= excludes labels= and needs mode 1")
+        if (tuple(targets.shape) != (B, S2) or targets.dtype != torch.float32
+                or not targets.is_contiguous()):
+            raise ValueError("policy_head_dual: targets must be contiguous fp32 [%d, %d]"
+                             % (B, S2))
+    if (tuple(zv.shape) != (B, S2) or zv.dtype != torch.float32 or not zv.is_contiguous()
+            or wv is None or wv.numel() < K or w.numel() < K):
+        raise ValueError("policy_head_dual: zv must be contiguous fp32 [%d, %d], w / wv [K]"
+                         % (B, S2))
+    _check(_lib().rag_policy_head_dual(
+        _ptr(h), _ptr(w), _ptr(b0), _ptr(pbias), _ptr(wv), _ptr(b0v), _ptr(probs), _ptr(zv),
+        _ptr(labels), _ptr(targets), _ptr(sweight), _ptr(loss), _ptr(dz), _ptr(hit),
+        _ptr(dzsum), B, S, KP, K, mode, float(gscale), _stream()), "policy_head_dual")
+
+
 def pass_grads(zout, dpass, dW, db):
     """PassLogit weight gradients on the GPU: dW = dpass^T zout ([S*S]), db = sum(dpass)."""
     B, P = zout.shape
@@ -576,6 +602,45 @@ def head_bwd(h, w, dz, dh, dw, db0, dpbias, K, relu_mask=True, work=None, metric
                                _ptr(dpbias), _ptr(work), B, S, KP, K, int(relu_mask),
                                _ptr(ml), _ptr(mh), _ptr(acc), _ptr(dzsum), _stream()),
            "head_bwd")
+
+
+_head2_ws = {}
+
+
+def head_bwd2(h, wp, wv, dzp, dzv, dh, dwp, dwv, db0p, db0v, dpbias, K, relu_mask=True,
+              work=None, metrics=None, dzsum=None):
+    """head_bwd for two 1x1 heads on one trunk output (policy wp / dzp, value wv / dzv): dH =
+    (dzp wp + dzv wv), ReLU-masked, written once; dwp, dwv, dpbias = sum_b dzp, db0p (from
+    ``dzsum`` when given, else from dzp), db0v = sum dzv. All overwritten, not accumulated;
+    ``metrics`` as head_bwd. h is read once."""
+    B, WP, _, KP = h.shape
+    S = WP - 2
+    for t in (dzp, dzv):
+        if t.dtype != torch.float32 or t.numel() != B * S * S or not t.is_contiguous():
+            raise ValueError("head_bwd2: dzp / dzv must be contiguous fp32 [B, S*S]")
+    if wp.numel() < K or wv.numel() < K or dwp.numel() < K or dwv.numel() < K:
+        raise ValueError("head_bwd2: weights and their gradients hold K = %d values" % K)
+    if dh is not None and (dh.shape != h.shape or dh.dtype != h.dtype):
+        raise ValueError("head_bwd2: dh must have h's layout")
+    need = _lib().rag_head_bwd2_workspace(B, S, KP)
+    if work is None:
+        work = _head2_ws.get(h.device)
+        if work is None or work.numel() < need:
+            work = torch.empty(need, dtype=torch.float32, device=h.device)
+            _head2_ws[h.device] = work
+    elif work.numel() < need:
+        raise ValueError("head_bwd2: work holds %d floats, %d needed" % (work.numel(), need))
+    ml = mh = acc = None
+    if metrics is not None:
+        ml, mh, acc = metrics
+        if acc.dtype != torch.float32 or acc.numel() < 2 or ml.numel() < B or mh.numel() < B:
+            raise ValueError("head_bwd2 metrics: loss [B], hit [B], fp32 acc [2]")
+    if dzsum is not None and dzsum.numel() < B:
+        raise ValueError("head_bwd2 dzsum: [B] per-board sums expected")
+    _check(_lib().rag_head_bwd2(_ptr(h), _ptr(wp), _ptr(wv), _ptr(dzp), _ptr(dzv), _ptr(dh),
+                                _ptr(dwp), _ptr(dwv), _ptr(db0p), _ptr(db0v), _ptr(dpbias),
+                                _ptr(work), B, S, KP, K, int(relu_mask), _ptr(ml), _ptr(mh),
+                                _ptr(acc), _ptr(dzsum), _stream()), "head_bwd2")
 
 
 def head_linear(h, w, b0, z, K):

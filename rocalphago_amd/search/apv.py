@@ -154,13 +154,25 @@ class _SlotResult(object):
                 s.o_sens[:n].numpy() if self.flags[2] else None)
 
 
+def is_dual(net):
+    """True for a policy-value network (models/policy_value.py): one trunk, both outputs."""
+    from ..models.policy_value import CNNPolicyValue
+    return isinstance(net, CNNPolicyValue)
+
+
 class NetworkEvaluator(object):
-    """Batched leaf evaluation: native boards -> (move priors [n, S*S], values [n])."""
+    """Batched leaf evaluation: native boards -> (move priors [n, S*S], values [n]). A
+    policy-value network as ``policy`` (and no ``value``) is both networks: one feature
+    extraction and ONE forward per wave fill priors and values (no side stream)."""
 
     def __init__(self, policy=None, value=None, nthreads=8, two_streams=True, graph=False,
                  wino_chain=False):
+        self.dual = is_dual(policy)
+        if self.dual and value is not None:
+            raise ValueError("a policy-value network is searched with its own value head: "
+                             "pass no separate value network")
         self.policy = policy
-        self.value = value
+        self.value = value = policy if self.dual else value
         # HipTrunk.wino_chain of this evaluator's plans (None: left as the trunks have it). Off
         # in the search: a chain block holds its CU for the whole run of layers (~0.5 ms)
         # instead of ~50 us, and the GPU rollout slices that share the chip no longer slip in
@@ -303,6 +315,11 @@ class NetworkEvaluator(object):
             gf.run(d["colors"][:n], d["ages"][:n], d["meta4"][:n], il,
                    d["ladders"][:n] if host_lad else None, n, S, out=x)
             slot.o_sens[:n].copy_(x[:, self._sens_off].reshape(n, -1), non_blocking=True)
+            if ppol is not None and ppol is pval:  # the policy-value network: one forward
+                pr, v = ppol.forward(x, clone=False)
+                slot.o_pri[:n].copy_(pr, non_blocking=True)
+                slot.o_val[:n].copy_(v, non_blocking=True)
+                return
             # the policy packer reads its first planes of the shared input in place
             side = None
             if ppol is not None and pval is not None and self.two_streams:
@@ -368,6 +385,8 @@ class NetworkEvaluator(object):
             xp, xv = (x[:, :self.npol].contiguous() if self.shared else x), x
         else:
             xp, xv = xs
+        if ppol is not None and ppol is pval:  # the policy-value network: one forward
+            return ppol.forward(xv)
         if ppol is not None and pval is not None and self.two_streams:
             # the value trunk on its own stream: its blocks fill the partial last block wave of
             # each policy conv (a B = 512 trunk conv is 964 blocks on 512 slots) and vice versa.
@@ -477,6 +496,10 @@ class NetworkEvaluator(object):
             sens = planes[:, off]
             sens = sens.reshape(n, -1).cpu().numpy() if not isinstance(sens, np.ndarray) \
                 else np.ascontiguousarray(sens.reshape(n, -1))
+        if self.dual:  # the policy-value network: one forward fills both outputs
+            pr, v = self.policy.model.predict(xv)
+            return (np.ascontiguousarray(pr, dtype=np.float32),
+                    np.ascontiguousarray(v, dtype=np.float32).reshape(-1), sens)
         if self.policy is not None:
             if isinstance(xp, np.ndarray):
                 xp = np.ascontiguousarray(xp)
@@ -493,7 +516,8 @@ class ParallelMCTS(object):
     """Wave-batched APV-MCTS over the native tree.
 
     policy: a CNNPolicy (priors); value: a CNNValue or None (then lmbda is forced to 1, i.e.
-    rollouts only); rollout: a ``_rocgo.RolloutPolicy`` (default weights if None).
+    rollouts only); a CNNPolicyValue as policy is both networks (no separate value then: one
+    evaluation per leaf); rollout: a ``_rocgo.RolloutPolicy`` (default weights if None).
     """
 
     def __init__(self, policy=None, value=None, rollout=None, lmbda=0.5, c_puct=5.0,
@@ -508,7 +532,10 @@ class ParallelMCTS(object):
         self.dp = dp if dp is not None and dp.enabled else None
         if self.dp is not None:
             seed = int(seed) + 7919 * self.dp.rank
-        if value is None and lmbda < 1:
+        if is_dual(policy) and value is not None:
+            raise ValueError("a policy-value network is searched with its own value head: "
+                             "pass no separate value network")
+        if value is None and not is_dual(policy) and lmbda < 1:
             lmbda = 1.0
         self.evaluator = evaluator or NetworkEvaluator(policy, value, nthreads)
         self.rollout = rollout or _rg.RolloutPolicy()

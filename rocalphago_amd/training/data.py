@@ -82,9 +82,11 @@ def soft_targets_np(visits, tf, table, classes):
 class DeviceDataset(object):
     """uint8 states [N, F, S, S] + flat action labels [N] resident on ``device``; optionally
     ``visits``: uint16 search visit counts [N, S*S] or [N, S*S + 1] (pass last), the dense policy
-    targets of ``--targets visits``."""
+    targets of ``--targets visits``, and ``outcomes``: fp32 [N, 1], the game's result for the
+    player to move (+1 / -1 / 0; training/search_data.py), the policy-value network's value
+    targets."""
 
-    def __init__(self, states, actions, device, board=None, visits=None):
+    def __init__(self, states, actions, device, board=None, visits=None, outcomes=None):
         states = np.asarray(states)
         self.N, self.F, self.S = states.shape[0], states.shape[1], states.shape[-1]
         acts = np.asarray(actions).astype(np.int64)
@@ -95,6 +97,12 @@ class DeviceDataset(object):
         self.labels = torch.from_numpy(labels).to(self.device)
         self.tf_table = torch.from_numpy(label_transform_table(self.S)).to(self.device)
         self._set_visits(visits)
+        self.outcomes = None
+        if outcomes is not None:
+            o = np.asarray(outcomes, dtype=np.float32).reshape(-1, 1)
+            if o.shape[0] != self.N:
+                raise ValueError("outcomes must hold %d values, got %d" % (self.N, o.shape[0]))
+            self.outcomes = torch.from_numpy(np.ascontiguousarray(o)).to(self.device)
 
     def _set_visits(self, visits):
         self.visits = None
@@ -104,12 +112,16 @@ class DeviceDataset(object):
     @classmethod
     def from_hdf5(cls, h5file, device):
         visits = h5file["visits"][()] if "visits" in h5file else None
-        return cls(h5file["states"][()], h5file["actions"][()], device, visits=visits)
+        outcomes = h5file["outcomes"][()] if "outcomes" in h5file else None
+        return cls(h5file["states"][()], h5file["actions"][()], device, visits=visits,
+                   outcomes=outcomes)
 
     @classmethod
-    def synthetic(cls, n, planes, board, device, seed=0, density=0.35, visits=False):
+    def synthetic(cls, n, planes, board, device, seed=0, density=0.35, visits=False,
+                  outcomes=False):
         """Random binary planes / uniform labels generated on the device (benchmarks); with
-        ``visits`` also visit rows [n, board^2 + 1]: ~40 random classes with counts below 64."""
+        ``visits`` also visit rows [n, board^2 + 1]: ~40 random classes with counts below 64;
+        with ``outcomes`` also random +1 / -1 game results [n, 1]."""
         g = torch.Generator(device=device)
         g.manual_seed(seed)
         ds = cls.__new__(cls)
@@ -127,6 +139,10 @@ class DeviceDataset(object):
             counts = counts * keep
             counts[torch.arange(n, device=device), ds.labels] += 64  # the move played leads
             ds.visits = counts.to(torch.int32).to(torch.uint16)
+        ds.outcomes = None
+        if outcomes:
+            ds.outcomes = (torch.randint(0, 2, (n, 1), generator=g, device=device) * 2
+                           - 1).float()
         return ds
 
     def batch_labels(self, index, tf):

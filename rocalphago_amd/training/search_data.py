@@ -3,7 +3,10 @@ the root's visit counts.
 
 The output is the SGF converter's dataset (``states`` uint8 [N, F, S, S], ``actions`` uint8
 [N, 2] = the move played, ``features``) plus ``visits``: uint16 [N, S*S + 1], the root children's
-visit counts of the search that chose the move (pass last, saturating at 65535). Training on the
+visit counts of the search that chose the move (pass last, saturating at 65535), and
+``outcomes``: int8 [N], the game's result for the player to move at that position (+1 won, -1
+lost, 0 drawn; the engine's ``get_winner()`` at the end of the game or at the move limit): the
+value targets of a policy-value network (``supervised.py`` with a CNNPolicyValue). Training on the
 normalised rows (``supervised.py --targets visits``) is the AlphaGo Zero / expert-iteration policy
 target; ``--targets actions`` on the same file trains on the moves alone. Positions where the move
 played is a pass are skipped, as the converter skips them.
@@ -41,7 +44,8 @@ def choose_move(row, rng, sample):
 
 
 def play_game(mcts, size, rng, temperature_moves=0, move_limit=None):
-    """One self-play game; returns the recorded (states, actions [n, 2], visits [n, S*S + 1])."""
+    """One self-play game; returns the recorded (states, actions [n, 2], visits [n, S*S + 1],
+    outcomes int8 [n]: the game's result for the player to move at each recorded position)."""
     P = size * size
     move_limit = move_limit or 2 * P
     state = go.GameState(size=size)
@@ -60,8 +64,11 @@ def play_game(mcts, size, rng, temperature_moves=0, move_limit=None):
         actions.append(move)
         rows.append(row)
         state.do_move(move)
+    winner = state.get_winner()
+    outcomes = np.asarray([0 if winner == 0 else (1 if st.current_player == winner else -1)
+                           for st in states], np.int8)
     return states, np.asarray(actions, np.uint8).reshape(-1, 2), \
-        np.asarray(rows, np.uint16).reshape(-1, P + 1)
+        np.asarray(rows, np.uint16).reshape(-1, P + 1), outcomes
 
 
 def generate_search_data(mcts, n_games, out_file, size=19, features=DEFAULT_FEATURES,
@@ -80,13 +87,17 @@ def generate_search_data(mcts, n_games, out_file, size=19, features=DEFAULT_FEAT
                               chunks=(1024, 2), compression="lzf")
         dv = f.create_dataset("visits", shape=(0, P1), dtype=np.uint16, maxshape=(None, P1),
                               chunks=(256, P1), compression="lzf")
+        do = f.create_dataset("outcomes", shape=(0,), dtype=np.int8, maxshape=(None,),
+                              chunks=(4096,), compression="lzf")
         f["features"] = np.bytes_(",".join(features))
         for g in range(n_games):
-            states, actions, rows = play_game(mcts, size, rng, temperature_moves, move_limit)
+            states, actions, rows, outcomes = play_game(mcts, size, rng, temperature_moves,
+                                                        move_limit)
             if states:
                 ds.append(pp.states_to_tensor_u8(states))
                 da.append(actions)
                 dv.append(rows)
+                do.append(outcomes)
                 n += len(states)
             if verbose:
                 print("game %d: %d positions (%d in all)" % (g, len(states), n))
@@ -104,7 +115,8 @@ def run(cmd_line_args=None):
                         help="Simulations per position. Default: 800")
     parser.add_argument("--size", type=int, default=19, help="Board size. Default: 19")
     parser.add_argument("--value", default=None,
-                        help="Path to a value model JSON (default: rollouts only)")
+                        help="Path to a value model JSON (default: rollouts only; omit it with "
+                             "a CNNPolicyValue policy, whose own value head is searched with)")
     parser.add_argument("--seed", type=int, default=0, help="Seed of the search and the sampling")
     parser.add_argument("--temperature-moves", type=int, default=0,
                         help="The first so many plies are drawn in proportion to the visit "
@@ -113,12 +125,15 @@ def run(cmd_line_args=None):
     args = parser.parse_args(cmd_line_args)
 
     from ..models.policy import CNNPolicy
+    from ..models.policy_value import CNNPolicyValue
     from ..models.value import CNNValue
     from ..search.apv import ParallelMCTS
     policy = CNNPolicy.load_model(args.policy)
     if policy.model.input_shape[-1] != args.size:
         raise ValueError("the policy plays %dx%d boards, --size is %d" %
                          (policy.model.input_shape[-1], policy.model.input_shape[-1], args.size))
+    if isinstance(policy, CNNPolicyValue) and args.value:
+        raise ValueError("a CNNPolicyValue policy searches with its own value head: omit --value")
     value = CNNValue.load_model(args.value) if args.value else None
     mcts = ParallelMCTS(policy, value, n_playout=args.playouts, seed=args.seed)
     n = generate_search_data(mcts, args.games, args.out_file, size=args.size,

@@ -196,6 +196,8 @@ class NativeSelfPlay(object):
         with torch.no_grad():
             probs = plan.forward(planes, clone=False) if plan is not None else \
                 policy.forward_device(planes)
+        if isinstance(probs, tuple):  # a policy-value network's plan: (probs, values)
+            probs = probs[0]
         sens = b["sens"][:n]
         if probs.shape[1] == P + 1:  # pass-logit network: pass is always a candidate
             sens = torch.cat([sens, torch.ones((n, 1), dtype=torch.uint8, device=self.device)],

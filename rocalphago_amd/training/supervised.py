@@ -24,6 +24,7 @@ from ..features.preprocessing import Preprocess
 from ..io import h5lite
 from ..models import kerasish as K
 from ..models.policy import CNNPolicy
+from ..models.policy_value import CNNPolicyValue
 from ..ops import hipops as ops
 from ..parallel.dp import BucketedAllReduce, DPContext
 from ..utils.metrics import RankMetrics
@@ -247,6 +248,144 @@ class SupervisedTrainer(object):
         return float(t[0] / max(t[2], 1)), float(t[1] / max(t[2], 1))
 
 
+NO_OUTCOMES = ("a policy-value network trains on a dataset with an 'outcomes' array (int8 [N]: "
+               "the game's result for the player to move; training/search_data.py writes one)")
+
+
+class PolicyValueTrainer(SupervisedTrainer):
+    """SupervisedTrainer for a CNNPolicyValue: the policy head on the dataset's moves or visit
+    distributions as before, the value head under ``value_weight`` * MSE on the dataset's
+    ``outcomes`` (invariant under the board symmetries). On the GPU one fused step
+    (fused.DualPlan.fwd_bwd); without a plan (CPU, fp32) ``train_on_batch(X, [Yp, Yv])``.
+    ``pop_metrics`` / ``evaluate`` return (policy loss, accuracy, value loss), the value loss
+    unweighted: mean((v - outcome)^2)."""
+
+    def __init__(self, model, dataset, batch_size, symmetries=None, dp=None, seed=0,
+                 metrics=None, targets="actions", value_weight=1.0):
+        if getattr(dataset, "outcomes", None) is None:
+            raise ValueError(NO_OUTCOMES)
+        if not value_weight > 0:
+            raise ValueError("value_weight must be > 0, got %r" % (value_weight,))
+        if model.n_outputs != 2:
+            raise ValueError("PolicyValueTrainer needs a two-output policy-value model")
+        self.value_weight = float(value_weight)
+        self.vloss_sum = torch.zeros((), device=dataset.device)
+        super(PolicyValueTrainer, self).__init__(
+            _PolicyOutput(model), dataset, batch_size, symmetries, dp,
+            loss="categorical_crossentropy", seed=seed, metrics=metrics, targets=targets)
+        self.model = model
+        if self.plan is not None and not getattr(self.plan, "multi_output", False):
+            self.plan = None
+
+    def step(self, index):
+        n = index.numel()
+        model = self.model
+        if self.plan is not None:
+            it = getattr(model.optimizer, "iterations", self.count)
+            labels = dense = None
+            if self.targets == "visits":
+                tf, dense = ops.sl_batch_soft(index.long().contiguous(), self.ds.visits,
+                                              self.ds.tf_table, self.sym, self.seed, it,
+                                              self.classes)
+            else:
+                tf, labels = ops.sl_batch(index.long().contiguous(), self.ds.labels,
+                                          self.ds.tf_table, self.sym, self.seed, it)
+            y = self.ds.outcomes[index]
+            B = self.plan.prepare(self.ds.states, index=index, transforms=tf)
+            hook = self.bucketer.layer_done if self.bucketer else None
+            lv = self.plan.fwd_bwd(B, labels, None, 1, 1.0 / B, y, self.value_weight,
+                                   on_layer_grads=hook, metrics=self.metric_acc, targets=dense)
+            self.vloss_sum += lv * n
+            if self.bucketer:
+                self.bucketer.finish()
+            model.optimizer.apply(model.net)
+        else:
+            X, Yp = self._host_batch(index, self._transforms(n))
+            Yv = self.ds.outcomes[index.to(self.ds.device)].cpu().numpy()
+            saved = model.grad_allreduce
+            if self.dp is not None and self.dp.enabled:
+                model.grad_allreduce = self.dp.allreduce_mean_
+            r = model.train_on_batch(X, [Yp, Yv])
+            model.grad_allreduce = saved
+            self.loss_sum += r[1] * n
+            self.vloss_sum += r[2] * n
+            self.hit_sum += (r[3] if len(r) > 3 else 0.0) * n
+        self.count += n
+        if self.metrics is not None:
+            self.metrics.step_done()
+
+    def pop_metrics(self):
+        """(mean policy loss, accuracy, mean value loss) since the last call, over all ranks."""
+        t = torch.stack([self.loss_sum + self.metric_acc[0], self.hit_sum + self.metric_acc[1],
+                         self.vloss_sum,
+                         torch.tensor(float(self.count), device=self.loss_sum.device)])
+        if self.dp is not None and self.dp.enabled:
+            self.dp.allreduce_sum_(t)
+        t = t.cpu().numpy()
+        self.loss_sum.zero_()
+        self.hit_sum.zero_()
+        self.vloss_sum.zero_()
+        self.metric_acc.zero_()
+        self.count = 0
+        d = max(t[3], 1)
+        return float(t[0] / d), float(t[1] / d), float(t[2] / d)
+
+    def evaluate(self, indices, batch=None):
+        """Validation (policy loss, accuracy, value loss) over dataset rows, no augmentation;
+        split over the ranks as SupervisedTrainer.evaluate."""
+        batch = batch or self.B
+        model = self.model
+        tot = torch.zeros(4, device=self.ds.device)
+        noop = torch.zeros(0, dtype=torch.int32, device=self.ds.device)
+        if self.dp is not None and self.dp.enabled:
+            indices = indices[self.dp.rank::self.dp.world]
+        for s in range(0, len(indices), batch):
+            idx = indices[s:s + batch]
+            y = self.ds.outcomes[idx]
+            if self.plan is not None:
+                B = self.plan.prepare(self.ds.states, index=idx)
+                self.plan.trunk.forward(B)
+                if self.targets == "visits":
+                    _, dense = ops.sl_batch_soft(idx.long().contiguous(), self.ds.visits,
+                                                 self.ds.tf_table, self.sym.new_zeros(1), 0, 0,
+                                                 self.classes)
+                    _, zv = self.plan._heads(B, targets=dense, mode=1, gscale=0.0)
+                else:
+                    _, zv = self.plan._heads(B, labels=self.ds.labels[idx], mode=1, gscale=0.0)
+                W1, b1, W2, b2 = self.plan._dense_params()
+                v = ops.value_mlp_fwd(zv, W1, b1, W2, b2, act=self.plan.act1)
+                tot[0] += self.plan.head.loss[:B].sum()
+                tot[1] += self.plan.head.hit[:B].sum()
+                tot[2] += ((v - y) ** 2).sum()
+                tot[3] += B
+            else:
+                X, Yp = self._host_batch(idx, noop.new_zeros(idx.numel()))
+                r = model.test_on_batch(X, [Yp, y.cpu().numpy()])
+                acc = r[3] if len(r) > 3 else 0.0
+                tot += torch.tensor([r[1] * len(X), acc * len(X), r[2] * len(X), len(X)],
+                                    device=tot.device)
+        if self.dp is not None and self.dp.enabled:
+            self.dp.allreduce_sum_(tot)
+        t = tot.cpu().numpy()
+        d = max(t[3], 1)
+        return float(t[0] / d), float(t[1] / d), float(t[2] / d)
+
+
+class _PolicyOutput(object):
+    """A two-output model as SupervisedTrainer's constructor reads it: the policy output's
+    shape, everything else the model's own."""
+
+    def __init__(self, model):
+        self._model = model
+
+    @property
+    def output_shape(self):
+        return self._model.output_shape[0]
+
+    def __getattr__(self, name):
+        return getattr(self._model, name)
+
+
 def run_training(cmd_line_args=None):
     """Run SL training; command-line args may be passed in as a list."""
     import argparse
@@ -266,6 +405,7 @@ def run_training(cmd_line_args=None):
     parser.add_argument("--symmetries", help="Comma-separated list of transforms, subset of noop,rot90,rot180,rot270,fliplr,flipud,diag1,diag2", default='noop,rot90,rot180,rot270,fliplr,flipud,diag1,diag2')  # noqa: E501
     parser.add_argument("--seed", help="RNG seed for shuffling / symmetries", type=int, default=None)  # noqa: E501
     parser.add_argument("--targets", help="Policy targets: actions (the move played, one-hot) or visits (the dataset's search visit counts, normalised; training/search_data.py writes them). Default: actions", choices=["actions", "visits"], default="actions")  # noqa: E501
+    parser.add_argument("--value-weight", help="Weight of the value head's MSE term in the loss of a policy-value network (CNNPolicyValue; its dataset needs 'outcomes'). An error for other models. Default: 1.0", type=float, default=None)  # noqa: E501
     parser.add_argument("--dtype", help="GPU compute precision: bf16 (fused HIP kernels) or fp32 (reference precision, generic executor). Default: bf16", choices=["bf16", "fp32"], default="bf16")  # noqa: E501
     if cmd_line_args is None:
         args = parser.parse_args()
@@ -287,6 +427,15 @@ def run_training(cmd_line_args=None):
     policy = CNNPolicy.load_model(args.model, device=dp.device).set_dtype(args.dtype)
     model_features = policy.preprocessor.feature_list
     model = policy.model
+    dual = isinstance(policy, CNNPolicyValue)
+    if args.value_weight is not None and not dual:
+        raise ValueError("--value-weight needs a policy-value network (CNNPolicyValue), %s is a "
+                         "%s" % (args.model, type(policy).__name__))
+    value_weight = 1.0 if args.value_weight is None else args.value_weight
+    if not dual:
+        del args.value_weight  # metadata.json of other models stays what it was
+    else:
+        args.value_weight = value_weight
     if resume:
         model.load_weights(os.path.join(args.out_directory, args.weights))
     dp.broadcast_model(model)
@@ -318,6 +467,8 @@ def run_training(cmd_line_args=None):
 
     if args.targets == "visits" and "visits" not in dataset:
         raise ValueError(NO_VISITS)
+    if dual and "outcomes" not in dataset:
+        raise ValueError(NO_OUTCOMES)
 
     n_total_data = len(dataset["states"])
     n_train_data = int(args.train_val_test[0] * n_total_data)
@@ -343,6 +494,8 @@ def run_training(cmd_line_args=None):
     meta_writer.metadata["training_data"] = args.train_data
     meta_writer.metadata["model_file"] = args.model
     meta_writer.metadata["targets"] = args.targets
+    if dual:
+        meta_writer.metadata["value_weight"] = value_weight
     meta_writer.metadata["cmd_line_args"] = meta_writer.metadata.get("cmd_line_args", [])
     meta_writer.metadata["cmd_line_args"].append(vars(args))
     meta_writer.set_model(model)
@@ -373,7 +526,11 @@ def run_training(cmd_line_args=None):
             raise ValueError("unknown symmetry %s" % s)
 
     sgd = K.SGD(lr=args.learning_rate, decay=args.decay)
-    model.compile(loss='categorical_crossentropy', optimizer=sgd, metrics=["accuracy"])
+    if dual:
+        model.compile(loss=['categorical_crossentropy', 'mse'], optimizer=sgd,
+                      loss_weights=[1.0, value_weight], metrics=["accuracy"])
+    else:
+        model.compile(loss='categorical_crossentropy', optimizer=sgd, metrics=["accuracy"])
     # exact resume: the optimizer step count (Keras decay schedule) and the data cursor live in
     # a sidecar next to each weights file (the reference does not save them)
     cursor = 0
@@ -390,8 +547,16 @@ def run_training(cmd_line_args=None):
     else:
         ds = DeviceDataset.from_hdf5(dataset, dp.device)
     rank_metrics = RankMetrics(args.out_directory, dp.rank, dp.world, dp.device)
-    trainer = SupervisedTrainer(model, ds, args.minibatch, symmetries, dp,
-                                seed=args.seed or 0, metrics=rank_metrics, targets=args.targets)
+    if dual:
+        if getattr(ds, "outcomes", None) is None:
+            raise ValueError(NO_OUTCOMES + " (not kept by --packed)")
+        trainer = PolicyValueTrainer(model, ds, args.minibatch, symmetries, dp,
+                                     seed=args.seed or 0, metrics=rank_metrics,
+                                     targets=args.targets, value_weight=value_weight)
+    else:
+        trainer = SupervisedTrainer(model, ds, args.minibatch, symmetries, dp,
+                                    seed=args.seed or 0, metrics=rank_metrics,
+                                    targets=args.targets)
     samples_per_epoch = args.epoch_length or n_train_data
     dev_train = torch.from_numpy(np.asarray(train_indices, dtype=np.int64)).to(dp.device)
     dev_val = torch.from_numpy(np.asarray(val_indices, dtype=np.int64)).to(dp.device)
@@ -416,13 +581,18 @@ def run_training(cmd_line_args=None):
             cursor = (cursor + gb) % n_train
             seen += args.minibatch
             heartbeat(sgd.iterations)
-        loss, acc = trainer.pop_metrics()
+        popped = trainer.pop_metrics()
+        loss, acc = popped[:2]
         dt = time.time() - t0
         rank_metrics.log(epoch=epoch_base + epoch, step=int(sgd.iterations))
         logs = {"loss": loss, "acc": acc}
+        if dual:
+            logs["value_loss"] = popped[2]
         if n_val_data > 0:
-            vl, va = trainer.evaluate(dev_val)
-            logs["val_loss"], logs["val_acc"] = vl, va
+            val = trainer.evaluate(dev_val)
+            logs["val_loss"], logs["val_acc"] = val[:2]
+            if dual:
+                logs["val_value_loss"] = val[2]
         gepoch = epoch_base + epoch
         # checkpoint (sidecar, then weights) before the metadata that records the epoch
         save_checkpoint(checkpointer, gepoch, logs,
