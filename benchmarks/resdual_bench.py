@@ -1,0 +1,196 @@
+"""The residual policy-value network (ResnetPolicyValue, fused.ResnetDualPlan): its fused SL
+step, the raw-top head kernels next to the ReLU pass they fold in, and the search.
+
+  python benchmarks/resdual_bench.py [--batch 256] [--filters 128] [--layers 20] [--steps 100]
+                                     [--playouts 8192] [--moves 6] [--skip-search]
+
+One JSON line:
+  * resdual_step_positions_per_s: PolicyValueTrainer.step (visit targets + outcomes, 49 planes)
+    at B x 19 x 19 under ResnetDualPlan.RAW_TOP as it stands, resdual_step_other_top the same
+    with the other setting, resnet_policy_step_positions_per_s the ResnetPolicy step
+    (SupervisedTrainer, visit targets, 48 planes) of the same width, all in this process;
+  * head_us[B] for B = 256 and 512 at K = --filters: the raw dual forward (labels) against
+    bn_apply(relu) + the plain dual forward, and raw head_bwd2 against bn_apply(relu) +
+    head_bwd2 (the pass is charged to the forward in the plan; here each pair carries it, so
+    the two rows bracket its cost). The candidates alternate in the same process
+    (dual_bench.alternate); ``spread`` is the largest max - min over a candidate's rounds;
+  * search_sims_per_s: ParallelMCTS(net, None) at mcts_bench.py --moves 6 --dual's geometry
+    (8192 playouts, waves of 512, lambda 0.5, GPU rollouts, from the empty board).
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+from benchmarks.dual_bench import alternate, timed  # noqa: E402
+from rocalphago_amd.ops import hipops as ops  # noqa: E402
+
+
+def alternate_with_spread(cands, rounds=7, iters=300, warmup=20):
+    """dual_bench.alternate's medians plus the largest max - min over a candidate's rounds
+    (one ``alternate`` round per call, so the candidates still take turns)."""
+    runs = {k: [] for k in cands}
+    for r in range(rounds):
+        one = alternate(cands, rounds=1, iters=iters, warmup=warmup if r == 0 else 2)
+        for k, v in one.items():
+            runs[k].append(v)
+    med = {k: round(statistics.median(v), 2) for k, v in runs.items()}
+    med["spread"] = round(max(max(v) - min(v) for v in runs.values()), 2)
+    return med
+
+
+def head_kernels(B, K, dev):
+    S, S2 = 19, 361
+    KP = ops.pad_channels(K)
+    a = ops.pack_nchw(torch.randn(B, K, S, S, device=dev), 1, KP)  # the last residual sum
+    h = ops.alloc_padded(B, S, 1, KP, dev)
+    g = torch.Generator(device=dev)
+    g.manual_seed(1)
+    wp, wv = (torch.randn(K, device=dev, generator=g) * 0.05 for _ in range(2))
+    b0, pb = torch.zeros(1, device=dev), torch.zeros(S2, device=dev)
+    lab = torch.randint(0, S2, (B,), device=dev, generator=g)
+    probs, dz, zv = (torch.empty(B, S2, device=dev) for _ in range(3))
+    loss, hit, dzsum = (torch.empty(B, device=dev) for _ in range(3))
+    kw = dict(labels=lab, mode=1, loss=loss, dz=dz, hit=hit, gscale=1.0 / B, dzsum=dzsum)
+
+    def relu_pass():
+        ops.bn_apply(a, h, B, S, K, coef=None, relu=True)
+
+    def mat_fwd():
+        relu_pass()
+        ops.policy_head_dual(h, wp, b0, pb, wv, b0, probs, zv, K, **kw)
+
+    fwd = alternate_with_spread({
+        "raw_dual_fwd": lambda: ops.policy_head_dual(a, wp, b0, pb, wv, b0, probs, zv, K,
+                                                     relu_in=True, **kw),
+        "relu_pass_plus_dual_fwd": mat_fwd,
+        "dual_fwd_alone": lambda: ops.policy_head_dual(h, wp, b0, pb, wv, b0, probs, zv, K, **kw),
+    })
+    dzv = torch.randn(B, S2, device=dev, generator=g) / B
+    dh = torch.zeros_like(h)
+    dwp, dwv = torch.empty(K, device=dev), torch.empty(K, device=dev)
+    dbp, dbv, dpb = torch.empty(1, device=dev), torch.empty(1, device=dev), torch.empty_like(pb)
+
+    def bwd2(src, relu_in):
+        ops.head_bwd2(src, wp, wv, dz, dzv, dh, dwp, dwv, dbp, dbv, dpb, K, dzsum=dzsum,
+                      relu_in=relu_in)
+
+    def mat_bwd():
+        relu_pass()
+        bwd2(h, False)
+
+    bwd = alternate_with_spread({
+        "raw_head_bwd2": lambda: bwd2(a, True),
+        "relu_pass_plus_head_bwd2": mat_bwd,
+        "head_bwd2_alone": lambda: bwd2(h, False),
+    })
+    return {"fwd": fwd, "bwd": bwd}
+
+
+def sl_steps(B, filters, layers, steps, warmup, dev):
+    from rocalphago_amd.features.preprocessing import DEFAULT_FEATURES, VALUE_FEATURES
+    from rocalphago_amd.models import kerasish as K
+    from rocalphago_amd.models.fused import ResnetDualPlan
+    from rocalphago_amd.models.policy import ResnetPolicy
+    from rocalphago_amd.models.policy_value import ResnetPolicyValue
+    from rocalphago_amd.training.data import TRANSFORM_NAMES, DeviceDataset
+    from rocalphago_amd.training.supervised import PolicyValueTrainer, SupervisedTrainer
+    kw = dict(board=19, filters_per_layer=filters, layers=layers, device=dev, seed=1)
+    n = 4 * B
+    out = {"raw_top": bool(ResnetDualPlan.RAW_TOP)}
+    index = [torch.randperm(n, device=dev)[:B] for _ in range(4)]
+
+    def rate(step):
+        k = [0]
+
+        def one():
+            step(index[k[0] % 4])
+            k[0] += 1
+        return round(B / (timed(one, steps, warmup) * 1e-6), 1)
+
+    ds = DeviceDataset.synthetic(n, 49, 19, dev, seed=3, visits=True, outcomes=True)
+    default = ResnetDualPlan.RAW_TOP
+    for key, raw in (("resdual_step_positions_per_s", default),
+                     ("resdual_step_other_top_positions_per_s", not default)):
+        ResnetDualPlan.RAW_TOP = raw
+        try:
+            dual = ResnetPolicyValue(VALUE_FEATURES, **kw).model
+            dual.compile(loss=["categorical_crossentropy", "mse"], optimizer=K.SGD(lr=0.003),
+                         metrics=["accuracy"])
+            tr = PolicyValueTrainer(dual, ds, B, TRANSFORM_NAMES, None, seed=1, targets="visits")
+        finally:
+            ResnetDualPlan.RAW_TOP = default
+        assert type(tr.plan) is ResnetDualPlan and tr.plan.trunk.top_relu_in == raw
+        out[key] = rate(tr.step)
+        m = tr.pop_metrics()
+        assert all(v == v for v in m), m
+        del tr, dual
+
+    pol = ResnetPolicy(DEFAULT_FEATURES, **kw).model
+    pol.compile(loss="categorical_crossentropy", optimizer=K.SGD(lr=0.003), metrics=["accuracy"])
+    dsp = DeviceDataset.synthetic(n, 48, 19, dev, seed=3, visits=True)
+    trp = SupervisedTrainer(pol, dsp, B, TRANSFORM_NAMES, None, seed=1, targets="visits")
+    assert trp.plan is not None, "HIP fused plan not active"
+    out["resnet_policy_step_positions_per_s"] = rate(trp.step)
+    return out
+
+
+def search(filters, layers, playouts, moves, dev):
+    """mcts_bench.measure's loop (it builds its own networks, so the loop is repeated here) on
+    a ParallelMCTS with the residual policy-value network."""
+    from rocalphago_amd.engine.gamestate import GameState
+    from rocalphago_amd.features.preprocessing import DEFAULT_FEATURES
+    from rocalphago_amd.models.policy_value import ResnetPolicyValue
+    from rocalphago_amd.search.apv import ParallelMCTS
+    net = ResnetPolicyValue(DEFAULT_FEATURES + ["color"], board=19, filters_per_layer=filters,
+                            layers=layers, device=dev, seed=1)
+    mc = ParallelMCTS(net, None, lmbda=0.5, batch=512, rollout_device="gpu", rollouts_per_leaf=1,
+                      nthreads=16, seed=1, pipeline=3, max_inflight=8, rollout_group=8)
+    mc.n_playout = playouts
+    st = GameState()
+    mc.search(st, 512)  # compiles / allocates; discarded tree
+    mc._search = None
+    mc.stats = {"waves": 0, "sims": 0}
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(moves):
+        mv = mc.get_move(st)
+        st.do_move(mv)
+        mc.update_with_move(mv)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    return {"search_sims_per_s": round(mc.stats["sims"] / dt, 1), "search_sims": mc.stats["sims"],
+            "search_moves": moves}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--filters", type=int, default=128)
+    ap.add_argument("--layers", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--playouts", type=int, default=8192)
+    ap.add_argument("--moves", type=int, default=6)
+    ap.add_argument("--skip-search", action="store_true")
+    ap.add_argument("--skip-steps", action="store_true")
+    args = ap.parse_args()
+    dev = torch.device("cuda")
+    res = {"metric": "residual policy-value network (19x19, B = %d, %d filters, %d layers)"
+           % (args.batch, args.filters, args.layers), "batch": args.batch}
+    res["head_us"] = {str(B): head_kernels(B, args.filters, dev) for B in (256, 512)}
+    if not args.skip_steps:
+        res.update(sl_steps(args.batch, args.filters, args.layers, args.steps, args.warmup, dev))
+    if not args.skip_search:
+        res.update(search(args.filters, args.layers, args.playouts, args.moves, dev))
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()

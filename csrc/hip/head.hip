@@ -47,7 +47,10 @@ struct HeadSoftmax {
 // DUAL (the policy-value network's shared trunk): a second 1x1 head on the same loaded channel
 // chunks, zv[b, p] = sum_k wv[k] H[b, p, k] + b0v (fp32 [B, S*S], no softmax); its weights sit
 // behind the first head's in ws (2 KP floats).
-template <bool DUAL = false>
+// RELU_IN (DUAL only; the residual trunk's raw top): H holds the last residual sum A_U, not
+// ReLU(A_U); each loaded channel value is clamped at 0 before both dot products. ReLU of a bf16
+// value is exact, so the results equal the plain form's on a materialised ReLU(A_U) bit for bit.
+template <bool DUAL = false, bool RELU_IN = false>
 __device__ __forceinline__ HeadSoftmax head_logits_softmax(
     const bf16* __restrict__ H, const float* __restrict__ w, const float* b0,
     const float* __restrict__ pbias, const float* __restrict__ pass_w,
@@ -76,11 +79,22 @@ __device__ __forceinline__ HeadSoftmax head_logits_softmax(
 #pragma unroll 4
       for (int c = sub * 8; c < KP; c += 64) {
         const bf16x8 v = *reinterpret_cast<const bf16x8*>(row + c);
+        if constexpr (RELU_IN) {
+          static_assert(DUAL, "the raw-top form exists for the two-head kernels only");
+          float hf[8];
 #pragma unroll
-        for (int t = 0; t < 8; ++t) acc += (float)v[t] * ws[c + t];
-        if constexpr (DUAL) {
+          for (int t = 0; t < 8; ++t) hf[t] = fmaxf((float)v[t], 0.f);
 #pragma unroll
-          for (int t = 0; t < 8; ++t) acv += (float)v[t] * ws[KP + c + t];
+          for (int t = 0; t < 8; ++t) acc += hf[t] * ws[c + t];
+#pragma unroll
+          for (int t = 0; t < 8; ++t) acv += hf[t] * ws[KP + c + t];
+        } else {
+#pragma unroll
+          for (int t = 0; t < 8; ++t) acc += (float)v[t] * ws[c + t];
+          if constexpr (DUAL) {
+#pragma unroll
+            for (int t = 0; t < 8; ++t) acv += (float)v[t] * ws[KP + c + t];
+          }
         }
       }
       acc += __shfl_xor(acc, 1);
@@ -124,7 +138,7 @@ __device__ __forceinline__ HeadSoftmax head_logits_softmax(
   return {gmax, 1.f / sum, mx, amax};
 }
 
-template <bool DUAL = false>
+template <bool DUAL = false, bool RELU_IN = false>
 __global__ void __launch_bounds__(kHeadFwdThreads)
 policy_head_fwd_kernel(const bf16* __restrict__ H, const float* __restrict__ w, const float* b0,
                        const float* __restrict__ pbias, float* __restrict__ probs,
@@ -144,8 +158,8 @@ policy_head_fwd_kernel(const bf16* __restrict__ H, const float* __restrict__ w, 
   const int S2 = S * S;
   const bool has_pass = pass_w != nullptr;
   const int C = S2 + (has_pass ? 1 : 0);
-  const HeadSoftmax sm = head_logits_softmax<DUAL>(H, w, b0, pbias, pass_w, pass_b, zout, z, ws,
-                                                   red, S, KP, K, wv, b0v, zv);
+  const HeadSoftmax sm = head_logits_softmax<DUAL, RELU_IN>(H, w, b0, pbias, pass_w, pass_b, zout,
+                                                            z, ws, red, S, KP, K, wv, b0v, zv);
   const float gmax = sm.gmax, inv = sm.inv, mx = sm.mx;
   const int amax = sm.amax;
   const int64_t lab = (mode && labels) ? labels[b] : -1;
@@ -222,7 +236,7 @@ policy_head_fwd_kernel(const bf16* __restrict__ H, const float* __restrict__ w, 
 // the label kernel's mode 1. hit = the lowest argmax of z is the lowest argmax of t.
 // One class per thread (C <= blockDim.x): the thread's target, probability and mask stay in
 // registers; one fused block reduction gives Tm, the loss and both argmaxes.
-template <bool DUAL = false>
+template <bool DUAL = false, bool RELU_IN = false>
 __global__ void __launch_bounds__(kHeadFwdThreads)
 policy_head_soft_kernel(const bf16* __restrict__ H, const float* __restrict__ w, const float* b0,
                         const float* __restrict__ pbias, float* __restrict__ probs,
@@ -247,8 +261,8 @@ policy_head_soft_kernel(const bf16* __restrict__ H, const float* __restrict__ w,
   const bool live = p < C;
   const float t = live ? targets[(size_t)b * C + p] : 0.f;
   const float tpass = has_pass ? targets[(size_t)b * C + S2] : 0.f;  // block-uniform
-  const HeadSoftmax sm = head_logits_softmax<DUAL>(H, w, b0, pbias, pass_w, pass_b, zout, z, ws,
-                                                   red, S, KP, K, w2, b02, z2);
+  const HeadSoftmax sm = head_logits_softmax<DUAL, RELU_IN>(H, w, b0, pbias, pass_w, pass_b, zout,
+                                                            z, ws, red, S, KP, K, w2, b02, z2);
   const float pr = live ? __expf(z[p] - sm.gmax) * sm.inv : 0.f;
   const float m = (pr >= 1e-7f && pr <= 1.f - 1e-7f) ? 1.f : 0.f;
   const float sw = sweight ? sweight[b] : 1.f;
@@ -413,7 +427,9 @@ head_bwd_kernel(const bf16* __restrict__ H, const float* __restrict__ w,
 // once, dH[b,p,k] = (dzp[b,p] wp[k] + dzv[b,p] wv[k]) (H[b,p,k] > 0) is written once, and the
 // block's partials of both weight gradients go to dwpart[blk][0][k] = sum_p dzp H[., k] and
 // dwpart[blk][1][k] = sum_p dzv H[., k] (rows of 2 KP floats).
-template <int CH>
+// RELU_IN (the residual trunk's raw top): H holds A_U, the dw sums run over max(A_U, 0) and the
+// mask is A_U > 0 whatever relu_mask says -- the plain form's results on ReLU(A_U), bit for bit.
+template <int CH, bool RELU_IN = false>
 __global__ void __launch_bounds__(kHeadThreads)
 head_bwd2_kernel(const bf16* __restrict__ H, const float* __restrict__ wp,
                  const float* __restrict__ wv, const float* __restrict__ dzp,
@@ -464,9 +480,10 @@ head_bwd2_kernel(const bf16* __restrict__ H, const float* __restrict__ wp,
         bf16x8 o;
 #pragma unroll
         for (int t = 0; t < 8; ++t) {
-          const float hf = (float)hv[u][t];
+          float hf = (float)hv[u][t];
           float d = g[u] * wl[t] + gv[u] * vl[t];
-          if (relu_mask && !(hf > 0.f)) d = 0.f;
+          if ((RELU_IN || relu_mask) && !(hf > 0.f)) d = 0.f;
+          if constexpr (RELU_IN) hf = fmaxf(hf, 0.f);
           o[t] = (bf16)d;
           dwa[t] += g[u] * hf;
           dva[t] += gv[u] * hf;
@@ -848,12 +865,13 @@ RAG_API int rag_policy_head_soft(const void* H, const float* w, const float* b0,
 // rag_policy_head_soft (categorical cross-entropy), without a pass logit and without in-kernel
 // metrics, plus the value head's 1x1 conv zv [B, S*S] = H . wv + b0v from the same loaded
 // channels. labels and targets exclude each other; targets need mode 1.
-RAG_API int rag_policy_head_dual(const void* H, const float* w, const float* b0,
-                                 const float* pbias, const float* wv, const float* b0v,
-                                 float* probs, float* zv, const int64_t* labels,
-                                 const float* targets, const float* sweight, float* loss,
-                                 float* dz, float* hit, float* dzsum, int B, int S, int KP, int K,
-                                 int mode, float gscale, hipStream_t stream) {
+template <bool RELU_IN>
+static int policy_head_dual_launch(const void* H, const float* w, const float* b0,
+                                   const float* pbias, const float* wv, const float* b0v,
+                                   float* probs, float* zv, const int64_t* labels,
+                                   const float* targets, const float* sweight, float* loss,
+                                   float* dz, float* hit, float* dzsum, int B, int S, int KP,
+                                   int K, int mode, float gscale, hipStream_t stream) {
   if (!H || !w || !wv || !zv || !probs || B <= 0 || S <= 0 || K <= 0 || K > KP || KP % 8)
     return -1;
   if (targets && (labels || mode != 1)) return -1;
@@ -861,14 +879,38 @@ RAG_API int rag_policy_head_dual(const void* H, const float* w, const float* b0,
   const size_t sm = (size_t)(((S * S + 4) & ~3) + 2 * KP) * sizeof(float);
   if (sm > 64 * 1024) return -1;
   if (targets)
-    policy_head_soft_kernel<true><<<B, kHeadFwdThreads, sm, stream>>>(
+    policy_head_soft_kernel<true, RELU_IN><<<B, kHeadFwdThreads, sm, stream>>>(
         (const bf16*)H, w, b0, pbias, probs, targets, sweight, loss, dz, hit, nullptr, nullptr,
         nullptr, nullptr, S, KP, K, gscale, dzsum, wv, b0v, zv);
   else
-    policy_head_fwd_kernel<true><<<B, kHeadFwdThreads, sm, stream>>>(
+    policy_head_fwd_kernel<true, RELU_IN><<<B, kHeadFwdThreads, sm, stream>>>(
         (const bf16*)H, w, b0, pbias, probs, labels, sweight, loss, dz, hit, nullptr, nullptr,
         nullptr, nullptr, nullptr, S, KP, K, mode, gscale, dzsum, wv, b0v, zv);
   return (int)hipGetLastError();
+}
+
+RAG_API int rag_policy_head_dual(const void* H, const float* w, const float* b0,
+                                 const float* pbias, const float* wv, const float* b0v,
+                                 float* probs, float* zv, const int64_t* labels,
+                                 const float* targets, const float* sweight, float* loss,
+                                 float* dz, float* hit, float* dzsum, int B, int S, int KP, int K,
+                                 int mode, float gscale, hipStream_t stream) {
+  return policy_head_dual_launch<false>(H, w, b0, pbias, wv, b0v, probs, zv, labels, targets,
+                                        sweight, loss, dz, hit, dzsum, B, S, KP, K, mode, gscale,
+                                        stream);
+}
+
+// rag_policy_head_dual on a raw trunk top: H is the residual trunk's last sum A_U and the kernels
+// clamp it at 0 in their loads (RELU_IN), so no ReLU(A_U) tensor is written for the heads.
+RAG_API int rag_policy_head_dual_relu(const void* H, const float* w, const float* b0,
+                                      const float* pbias, const float* wv, const float* b0v,
+                                      float* probs, float* zv, const int64_t* labels,
+                                      const float* targets, const float* sweight, float* loss,
+                                      float* dz, float* hit, float* dzsum, int B, int S, int KP,
+                                      int K, int mode, float gscale, hipStream_t stream) {
+  return policy_head_dual_launch<true>(H, w, b0, pbias, wv, b0v, probs, zv, labels, targets,
+                                       sweight, loss, dz, hit, dzsum, B, S, KP, K, mode, gscale,
+                                       stream);
 }
 
 // mloss / mhit / acc (optional): the head forward's per-board loss and top-1 hit (written with
@@ -912,11 +954,12 @@ RAG_API size_t rag_head_bwd_workspace(int B, int S, int KP) {
 // overwritten): dH = (dzp wp + dzv wv) (H > 0 or no mask) written once, dwp, dwv, dpbias =
 // sum_b dzp, db0p = sum dzsum (or sum dzp), db0v = sum dzv; mloss / mhit / acc as rag_head_bwd.
 // work: >= rag_head_bwd2_workspace(B, S, KP) floats. dH and dpbias are optional.
-RAG_API int rag_head_bwd2(const void* H, const float* wp, const float* wv, const float* dzp,
-                          const float* dzv, void* dH, float* dwp, float* dwv, float* db0p,
-                          float* db0v, float* dpbias, float* work, int B, int S, int KP, int K,
-                          int relu_mask, const float* mloss, const float* mhit, float* acc,
-                          const float* dzsum, hipStream_t stream) {
+template <bool RELU_IN>
+static int head_bwd2_launch(const void* H, const float* wp, const float* wv, const float* dzp,
+                            const float* dzv, void* dH, float* dwp, float* dwv, float* db0p,
+                            float* db0v, float* dpbias, float* work, int B, int S, int KP, int K,
+                            int relu_mask, const float* mloss, const float* mhit, float* acc,
+                            const float* dzsum, hipStream_t stream) {
   if (!H || !wp || !wv || !dzp || !dzv || !dwp || !dwv || !db0p || !db0v || !work) return -1;
   if (B <= 0 || S <= 0 || K <= 0 || K > KP) return -1;
   if (acc && (!mloss || !mhit)) return -1;
@@ -926,9 +969,8 @@ RAG_API int rag_head_bwd2(const void* H, const float* wp, const float* wv, const
   const int ppb = (npix + nblk - 1) / nblk;
 #define RAG_HB2(C)                                                                            \
   case C:                                                                                     \
-    head_bwd2_kernel<C><<<nblk, kHeadThreads, 0, stream>>>((const bf16*)H, wp, wv, dzp, dzv,  \
-                                                           (bf16*)dH, work, npix, ppb, S, K,  \
-                                                           relu_mask);                        \
+    head_bwd2_kernel<C, RELU_IN><<<nblk, kHeadThreads, 0, stream>>>(                          \
+        (const bf16*)H, wp, wv, dzp, dzv, (bf16*)dH, work, npix, ppb, S, K, relu_mask);       \
     break;
   switch (KP % 8 ? 0 : KP / 8) {
     RAG_HB2(4) RAG_HB2(8) RAG_HB2(12) RAG_HB2(16) RAG_HB2(24) RAG_HB2(32) RAG_HB2(48) RAG_HB2(64)
@@ -940,6 +982,26 @@ RAG_API int rag_head_bwd2(const void* H, const float* wp, const float* wv, const
       work, dzp, dwp, db0p, dpbias, nblk, B, S * S, KP, K, mloss, mhit, acc, dzsum, dzv, dwv,
       db0v);
   return (int)hipGetLastError();
+}
+
+RAG_API int rag_head_bwd2(const void* H, const float* wp, const float* wv, const float* dzp,
+                          const float* dzv, void* dH, float* dwp, float* dwv, float* db0p,
+                          float* db0v, float* dpbias, float* work, int B, int S, int KP, int K,
+                          int relu_mask, const float* mloss, const float* mhit, float* acc,
+                          const float* dzsum, hipStream_t stream) {
+  return head_bwd2_launch<false>(H, wp, wv, dzp, dzv, dH, dwp, dwv, db0p, db0v, dpbias, work, B,
+                                 S, KP, K, relu_mask, mloss, mhit, acc, dzsum, stream);
+}
+
+// rag_head_bwd2 on a raw trunk top (H = A_U, see rag_policy_head_dual_relu): the mask A_U > 0 is
+// always applied and the weight gradients sum over max(A_U, 0). Workspace as rag_head_bwd2.
+RAG_API int rag_head_bwd2_relu(const void* H, const float* wp, const float* wv, const float* dzp,
+                               const float* dzv, void* dH, float* dwp, float* dwv, float* db0p,
+                               float* db0v, float* dpbias, float* work, int B, int S, int KP,
+                               int K, const float* mloss, const float* mhit, float* acc,
+                               const float* dzsum, hipStream_t stream) {
+  return head_bwd2_launch<true>(H, wp, wv, dzp, dzv, dH, dwp, dwv, db0p, db0v, dpbias, work, B, S,
+                                KP, K, 1, mloss, mhit, acc, dzsum, stream);
 }
 
 RAG_API size_t rag_head_bwd2_workspace(int B, int S, int KP) {

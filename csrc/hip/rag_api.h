@@ -99,6 +99,17 @@ RAG_API int rag_head_bwd2(const void* H, const float* wp, const float* wv, const
                           int relu_mask, const float* mloss, const float* mhit, float* acc,
                           const float* dzsum, hipStream_t stream);
 RAG_API size_t rag_head_bwd2_workspace(int B, int S, int KP);
+RAG_API int rag_policy_head_dual_relu(const void* H, const float* w, const float* b0,
+                                      const float* pbias, const float* wv, const float* b0v,
+                                      float* probs, float* zv, const int64_t* labels,
+                                      const float* targets, const float* sweight, float* loss,
+                                      float* dz, float* hit, float* dzsum, int B, int S, int KP,
+                                      int K, int mode, float gscale, hipStream_t stream);
+RAG_API int rag_head_bwd2_relu(const void* H, const float* wp, const float* wv, const float* dzp,
+                               const float* dzv, void* dH, float* dwp, float* dwv, float* db0p,
+                               float* db0v, float* dpbias, float* work, int B, int S, int KP,
+                               int K, const float* mloss, const float* mhit, float* acc,
+                               const float* dzsum, hipStream_t stream);
 RAG_API int rag_head_linear(const void* H, const float* w, const float* b0, float* z, int B,
                             int S, int KP, int K, hipStream_t stream);
 RAG_API size_t rag_value_mlp_workspace(int B, int H);

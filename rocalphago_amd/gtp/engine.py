@@ -468,7 +468,7 @@ def main(argv=None):
     ap.add_argument("--dtype", choices=["bf16", "fp32"], default="bf16",
                     help="GPU compute precision of the networks (bf16 = fused HIP kernels)")
     ap.add_argument("--value", default=None,
-                    help="value network JSON (mcts player; omit it with a CNNPolicyValue model, "
+                    help="value network JSON (mcts player; omit it with a policy-value model, "
                          "whose own value head is searched with)")
     ap.add_argument("--value-weights", default=None)
     ap.add_argument("--lmbda", type=float, default=None,

@@ -451,16 +451,14 @@ class BNSpec(object):
 
 
 class ResTrunk(_PackedConvs):
-    # 3x3 128 -> 128 layers whose input BN is fused run the Winograd BN kernel: "0" off, "1"
-    # forward only (default), "2" forward and dgrad (see __init__)
-    WINO_MODE = "1"
-    DEFER_REDUCE = True
-
     """Residual trunk of ResnetPolicy (reference policy.py:196-244) on the HIP engine:
 
         A_0 = conv0(x)                                       (linear, 5x5 by default)
         unit u: X = A_u; n_skip x [U = ReLU(BN(X)); X = conv(U)]; A_{u+1} = A_u + X
         H = ReLU(A_U)                                        (read by the policy head)
+
+    ``raw_top=True`` (the two-head plan, whose head kernels clamp at 0 in their loads) leaves
+    H unwritten: ``output`` is A_U itself and ``top_relu_in`` tells the head engine so.
 
     Forward: the column BN statistics (summed in the epilogue of the fused conv that produced
     the BN input, else a bn.hip pass) + a finalize launch, then BN+ReLU fused into the next
@@ -478,11 +476,18 @@ class ResTrunk(_PackedConvs):
     5x5 by default). Memory: (units + BNs + ~4) activations of B x (S+2)^2 x K bf16 (29 MB each
     at B=256, K=128) — trivial against 288 GB of HBM."""
 
-    def __init__(self, specs, units, bns, board, device):
+    # 3x3 128 -> 128 layers whose input BN is fused run the Winograd BN kernel: "0" off, "1"
+    # forward only (default), "2" forward and dgrad (see __init__)
+    WINO_MODE = "1"
+    DEFER_REDUCE = True
+
+    def __init__(self, specs, units, bns, board, device, raw_top=False):
         assert specs and len(specs) == 1 + sum(units) == 1 + len(bns)
         self.specs, self.units, self.bns = specs, list(units), bns
         self.S = board
         self.device = device
+        # the head reads A_U and applies the ReLU itself: no H = ReLU(A_U) pass
+        self.top_relu_in = bool(raw_top)
         self.L = len(specs)
         K = specs[0].cout
         for s in specs[1:]:
@@ -563,7 +568,7 @@ class ResTrunk(_PackedConvs):
         return self.xin[:B]
 
     def output(self, B):
-        return self.H[:B]
+        return self.A[-1][:B] if self.top_relu_in else self.H[:B]
 
     top_relu = True
 
@@ -649,8 +654,9 @@ class ResTrunk(_PackedConvs):
                     ops.conv_igemm(U, self._wf[l], self._bias[l], y, B, S, self.hin[l], 1,
                                    sp.cinp, sp.coutp, sp.ks, False, residual=res)
                 j += 1
-        ops.bn_apply(self.A[-1][:B], self.H[:B], B, S, K, coef=None, relu=True)
-        return self.H[:B]
+        if not self.top_relu_in:
+            ops.bn_apply(self.A[-1][:B], self.H[:B], B, S, K, coef=None, relu=True)
+        return self.output(B)
 
     def backward(self, B, dws, dbs, top_which=0, accumulate=False, on_layer_done=None):
         """Backprop from top_grad (dL/dA_U, already ReLU-masked by the head) to conv0; writes
@@ -908,7 +914,8 @@ class DualHeadEngine(object):
                              sweight=sweight, loss=self.loss[:B] if mode else None,
                              dz=self.dz[:B] if mode else None,
                              hit=self.hit[:B] if mode else None, mode=mode, gscale=gscale,
-                             dzsum=self.dzsum[:B] if mode else None)
+                             dzsum=self.dzsum[:B] if mode else None,
+                             relu_in=getattr(self.trunk, "top_relu_in", False))
         self._macc = acc if mode else None
         return self.probs[:B], self.zv[:B]
 
@@ -923,4 +930,4 @@ class DualHeadEngine(object):
                       self.trunk.top_grad(B), dw, dwv, db0, db0v, dpbias, self.K,
                       relu_mask=self.trunk.top_relu,
                       metrics=(self.loss[:B], self.hit[:B], acc) if acc is not None else None,
-                      dzsum=self.dzsum[:B])
+                      dzsum=self.dzsum[:B], relu_in=getattr(self.trunk, "top_relu_in", False))

@@ -12,6 +12,8 @@
   DualPlan:    (functional, two outputs) [Conv2D 'same' + ReLU]* -> the PolicyPlan head (no pass
                logit, output 0) and the ValuePlan head (output 1) on the same trunk output
                                                        (CNNPolicyValue, models/policy_value.py)
+  ResnetDualPlan: (functional, two outputs) ResnetPlan's residual trunk up to its final ReLU ->
+               DualPlan's two heads             (ResnetPolicyValue, models/policy_value.py)
 
 and executes them on the HIP engine (models/engine.py): one packed-input kernel (uint8 or fp32
 planes, optional gather + dihedral transform), one MFMA conv launch per layer, the fused head
@@ -36,7 +38,7 @@ def _conv_ok(ld):
 def detect_plan(model):
     if model.functional:
         if len(model.net.output_names) > 1:
-            return _detect_dual(model)
+            return _detect_dual(model) or _detect_resnet_dual(model)
         return _detect_resnet(model)
     L = model.layers
     n = 0
@@ -67,7 +69,10 @@ def detect_plan(model):
 
 
 class _TrunkPlan(object):
-    def __init__(self, model, convs, head_conv):
+    def __init__(self, model, convs, head_conv, res=None):
+        """res: None for a straight run of convolutions (HipTrunk), or (bns, units, raw_top) for
+        the residual trunk (ResTrunk: BatchNormalization layers, convs per unit, and whether
+        the head reads the last residual sum itself)."""
         net = model.net
         self.model = model
         self.net = net
@@ -77,7 +82,13 @@ class _TrunkPlan(object):
             specs.append(ConvSpec(ld.config["nb_row"], W.shape[1], W.shape[0],
                                   ld.config.get("activation", "linear") == "relu"))
         self.S = model.input_shape[-1]
-        self.trunk = HipTrunk(specs, self.S, net.device)
+        if res is None:
+            self.trunk = HipTrunk(specs, self.S, net.device)
+        else:
+            bns, units, raw_top = res
+            bspecs = [BNSpec(ld.config.get("epsilon", 1e-3), ld.config.get("momentum", 0.99),
+                             net.params_of(ld.name), net.grads_of(ld.name)) for ld in bns]
+            self.trunk = ResTrunk(specs, units, bspecs, self.S, net.device, raw_top=raw_top)
         self.conv_names = [ld.name for ld in convs]
         self.head_name = head_conv.name
         self.K = specs[-1].cout
@@ -307,9 +318,19 @@ def _detect_dual(model):
             and _conv_ok(L[n]) and L[n].config.get("activation") == "relu":
         n += 1
     convs, rest = L[1:n], L[n:]
-    if not convs or convs[-1].config["nb_row"] > 3 or len(rest) != 8:
+    if not convs or convs[-1].config["nb_row"] > 3:
         return None
-    top = convs[-1].name
+    heads = _match_two_heads(model, rest, convs[-1].name)
+    return DualPlan(model, convs, *heads) if heads else None
+
+
+def _match_two_heads(model, rest, top):
+    """The policy-value heads on the layer named ``top``: ``rest`` is exactly the policy branch
+    (Conv 1x1 -> Flatten -> Bias -> softmax, output 0) then the value branch (Conv 1x1 ->
+    Flatten -> Dense -> Dense(1, tanh), output 1). Returns (policy conv, Bias, value conv,
+    Dense, Dense) or None."""
+    if len(rest) != 8:
+        return None
 
     def head_conv(ld):
         c = ld.config
@@ -332,7 +353,7 @@ def _detect_dual(model):
         return None
     if list(model.net.output_names) != [pol[3].name, val[3].name]:
         return None
-    return DualPlan(model, convs, pol[0], pol[2], val[0], val[2], val[3])
+    return pol[0], pol[2], val[0], val[2], val[3]
 
 
 class DualPlan(_TrunkPlan):
@@ -344,8 +365,9 @@ class DualPlan(_TrunkPlan):
     pass_name = None
     loss_mode = staticmethod(PolicyPlan.loss_mode)
 
-    def __init__(self, model, convs, head_conv, bias_layer, vhead_conv, dense1, dense2):
-        super(DualPlan, self).__init__(model, convs, head_conv)
+    def __init__(self, model, convs, head_conv, bias_layer, vhead_conv, dense1, dense2,
+                 res=None):
+        super(DualPlan, self).__init__(model, convs, head_conv, res=res)
         self.bias_name = bias_layer.name
         self.vhead_name = vhead_conv.name
         self.d1, self.d2 = dense1.name, dense2.name
@@ -440,26 +462,31 @@ class DualPlan(_TrunkPlan):
         return lossv.detach()
 
 
-def _detect_resnet(model):
-    """Match ResnetPolicy's functional graph (topologically ordered layer list)."""
+def _linear_conv(ld, src, ks=None):
+    return (_conv_ok(ld) and ld.inbound == [src] and
+            ld.config.get("activation", "linear") == "linear" and
+            (ks is None or ld.config["nb_row"] == ks))
+
+
+def _act(ld, src, name):
+    return (ld.class_name == "Activation" and ld.inbound == [src] and
+            ld.config["activation"] == name)
+
+
+def _match_res_trunk(model):
+    """The residual trunk both ResNet plans share, up to and including its final ReLU (a
+    topologically ordered layer list): (convs, bns, units, the ReLU's name, the layers behind
+    it), or None."""
     L = model.layers
     S = model.input_shape[-1] if model.input_shape else None
     if not S or S > 25 or len(L) < 8 or L[0].class_name != "InputLayer":
         return None
-
-    def conv(ld, src, ks=None):
-        return (_conv_ok(ld) and ld.inbound == [src] and
-                ld.config.get("activation", "linear") == "linear" and
-                (ks is None or ld.config["nb_row"] == ks))
+    conv, act = _linear_conv, _act
 
     def bn_ok(ld, src):
         c = ld.config
         return (ld.class_name == "BatchNormalization" and ld.inbound == [src] and
                 c.get("mode", 0) == 0 and c.get("axis", -1) in (-1, 3))
-
-    def act(ld, src, name):
-        return (ld.class_name == "Activation" and ld.inbound == [src] and
-                ld.config["activation"] == name)
 
     if not conv(L[1], L[0].name):
         return None
@@ -480,19 +507,39 @@ def _detect_resnet(model):
             return None
         units.append(n)
         cur, i = m.name, i + 1
-    rest = L[i:]
-    pl = rest[4] if len(rest) == 6 and rest[4].class_name == "PassLogit" and \
-        rest[4].inbound == [rest[3].name] else None
-    if not units or len(rest) != (6 if pl is not None else 5) or \
-            not act(rest[0], cur, "relu") or \
-            not conv(rest[1], rest[0].name, 1) or rest[1].config["nb_filter"] != 1 or \
-            rest[2].class_name != "Flatten" or rest[3].class_name != "Bias" or \
-            not act(rest[-1], rest[-2].name, "softmax"):
+    if not units or i >= len(L) or not act(L[i], cur, "relu"):
         return None
     K = L[1].config["nb_filter"]
     if any(c.config["nb_filter"] != K for c in convs):
         return None
-    return ResnetPlan(model, convs, bns, units, rest[1], rest[3], pl)
+    return convs, bns, units, L[i].name, L[i + 1:]
+
+
+def _detect_resnet(model):
+    """Match ResnetPolicy's functional graph (topologically ordered layer list)."""
+    m = _match_res_trunk(model)
+    if m is None:
+        return None
+    convs, bns, units, top, rest = m
+    pl = rest[3] if len(rest) == 5 and rest[3].class_name == "PassLogit" and \
+        rest[3].inbound == [rest[2].name] else None
+    if len(rest) != (5 if pl is not None else 4) or \
+            not _linear_conv(rest[0], top, 1) or rest[0].config["nb_filter"] != 1 or \
+            rest[1].class_name != "Flatten" or rest[2].class_name != "Bias" or \
+            not _act(rest[-1], rest[-2].name, "softmax"):
+        return None
+    return ResnetPlan(model, convs, bns, units, rest[0], rest[2], pl)
+
+
+def _detect_resnet_dual(model):
+    """Match ResnetPolicyValue's functional graph: ResnetPolicy's trunk up to its final ReLU,
+    then CNNPolicyValue's two heads on it; anything else runs the generic executor."""
+    m = _match_res_trunk(model)
+    if m is None or model.input_shape[-2] != model.input_shape[-1]:
+        return None
+    convs, bns, units, top, rest = m
+    heads = _match_two_heads(model, rest, top)
+    return ResnetDualPlan(model, convs, bns, units, *heads) if heads else None
 
 
 class ResnetPlan(PolicyPlan):
@@ -502,20 +549,27 @@ class ResnetPlan(PolicyPlan):
     like Keras' learning phase."""
 
     def __init__(self, model, convs, bns, units, head_conv, bias_layer, pass_layer=None):
-        net = model.net
-        self.model, self.net = model, net
-        specs = []
-        for ld in convs:
-            W = net.params_of(ld.name)[0]
-            specs.append(ConvSpec(ld.config["nb_row"], W.shape[1], W.shape[0], False))
-        bspecs = [BNSpec(ld.config.get("epsilon", 1e-3), ld.config.get("momentum", 0.99),
-                         net.params_of(ld.name), net.grads_of(ld.name)) for ld in bns]
-        self.S = model.input_shape[-1]
-        self.trunk = ResTrunk(specs, units, bspecs, self.S, net.device)
-        self.conv_names = [ld.name for ld in convs]
-        self.head_name = head_conv.name
-        self.K = specs[-1].cout
-        net._sgd_fold = self.sgd_fold  # the optimizer's step folded into the weight repack
+        _TrunkPlan.__init__(self, model, convs, head_conv, res=(bns, units, False))
         self.bias_name = bias_layer.name
         self.pass_name = pass_layer.name if pass_layer is not None else None
         self.head = PolicyHeadEngine(self.trunk, self.K, pass_logit=pass_layer is not None)
+
+
+class ResnetDualPlan(DualPlan):
+    """ResnetPolicyValue on the HIP engine: ResnetPlan's ResTrunk under DualPlan's two heads
+    (every method is DualPlan's: they touch only ``self.trunk`` and ``self.head``). Training
+    steps use batch statistics and update the running averages; forward / evaluation use the
+    running ones, as ResnetPlan."""
+
+    # True: the head kernels read the last residual sum A_U and clamp it at 0 in their loads
+    # (ops.policy_head_dual / head_bwd2 relu_in) instead of a ReLU(A_U) tensor written by one
+    # more whole-tensor launch. Bit-identical results either way; an A/B switch. Measured
+    # (benchmarks/resdual_bench.py, K = 128, candidates alternating, spread between rounds
+    # <= 0.5 us): forward 10.7 us against 22.7 us with the pass at B = 256, 22.1 against 38.5
+    # at B = 512; head_bwd2 18.3 / 30.2 us raw against 19.2 / 31.6 on the materialised tensor.
+    RAW_TOP = True
+
+    def __init__(self, model, convs, bns, units, head_conv, bias_layer, vhead_conv, dense1,
+                 dense2):
+        super(ResnetDualPlan, self).__init__(model, convs, head_conv, bias_layer, vhead_conv,
+                                             dense1, dense2, res=(bns, units, self.RAW_TOP))

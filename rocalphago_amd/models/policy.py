@@ -92,6 +92,23 @@ class ResnetPolicy(CNNPolicy):
         }
         params = defaults
         params.update(kwargs)
+        layers, add, inp, path = ResnetPolicy._trunk(params)
+        path = add(K.Convolution2D(nb_filter=1, nb_row=1, nb_col=1, init='uniform',
+                                   border_mode='same'), [path])
+        path = add(K.Flatten(), [path])
+        path = add(Bias(), [path])
+        if params.get("pass_logit"):
+            path = add(K.PassLogit(), [path])
+        out = add(K.Activation('softmax'), [path])
+        return K.Model(layers, functional=True, inputs=[inp.name], outputs=[out],
+                       device=params.get("device"), seed=params.get("seed"))
+
+    @staticmethod
+    def _trunk(params):
+        """The residual trunk up to and including its final ReLU: (layers, add, the input
+        layer, the ReLU's name). ``add(layer, inbound)`` appends to ``layers``; the policy-value
+        network (models/policy_value.py ResnetPolicyValue) puts its two heads on the same
+        trunk."""
         layers = []
 
         def add(layer, inbound):
@@ -134,15 +151,7 @@ class ResnetPolicy(CNNPolicy):
             warnings.warn("ResnetPolicy: n_skip settings give %d layers (%d requested)"
                           % (layer, params['layers']))
         path = add(K.Activation('relu'), [path])
-        path = add(K.Convolution2D(nb_filter=1, nb_row=1, nb_col=1, init='uniform',
-                                   border_mode='same'), [path])
-        path = add(K.Flatten(), [path])
-        path = add(Bias(), [path])
-        if params.get("pass_logit"):
-            path = add(K.PassLogit(), [path])
-        out = add(K.Activation('softmax'), [path])
-        return K.Model(layers, functional=True, inputs=[inp.name], outputs=[out],
-                       device=params.get("device"), seed=params.get("seed"))
+        return layers, add, inp, path
 
 
 def has_pass_logit(policy):

@@ -13,13 +13,18 @@ this layer order (trunk parameters first in ``net.flat``):
 On a GPU the whole network runs on the fused HIP plan (models/fused.py DualPlan): one trunk
 pass, one head launch for both heads, one backward launch that writes the trunk-top gradient of
 both heads once.
+
+``ResnetPolicyValue`` puts the same two heads on ResnetPolicy's residual trunk (its layer list up
+to and including the final ReLU; fused.ResnetDualPlan on a GPU). Layers are appended trunk,
+policy branch, value branch, so the leading weight arrays are a ResnetPolicy's of the same
+arguments.
 """
 import numpy as np
 
 from ..features.preprocessing import VALUE_FEATURES
 from . import kerasish as K
 from .nn_util import Bias, neuralnet
-from .policy import CNNPolicy
+from .policy import CNNPolicy, ResnetPolicy
 
 
 @neuralnet
@@ -95,6 +100,12 @@ class CNNPolicyValue(CNNPolicy):
             nf = params.get("filters_per_layer_%d" % i, params["filters_per_layer"])
             path = add(K.Convolution2D(nb_filter=nf, nb_row=fw, nb_col=fw, init='uniform',
                                        activation='relu', border_mode='same'), [path])
+        return CNNPolicyValue._two_heads(layers, add, inp, path, params)
+
+    @staticmethod
+    def _two_heads(layers, add, inp, path, params):
+        """The policy branch (output 0), then the value branch (output 1), on the trunk output
+        ``path``; returns the Model."""
         p = add(K.Convolution2D(nb_filter=1, nb_row=1, nb_col=1, init='uniform',
                                 border_mode='same'), [path])
         p = add(K.Flatten(), [p])
@@ -108,3 +119,23 @@ class CNNPolicyValue(CNNPolicy):
         v = add(K.Dense(1, init='uniform', activation='tanh'), [v])
         return K.Model(layers, functional=True, inputs=[inp.name], outputs=[p, v],
                        device=params.get("device"), seed=params.get("seed"))
+
+
+@neuralnet
+class ResnetPolicyValue(CNNPolicyValue):
+    """Residual policy-value network: ResnetPolicy's trunk (linear input conv, units of
+    n_skip_K x (BatchNorm -> ReLU -> conv) with sum-merge, final ReLU) under CNNPolicyValue's
+    two heads."""
+
+    @staticmethod
+    def create_network(**kwargs):
+        """ResnetPolicy's keyword args: input_dim, board (19), filters_per_layer (128), layers
+        (20), filter_width_1 (5), n_skip_K, filter_width_K; the value head's: dense (256),
+        dense_activation ("relu"); device, seed. No pass logit."""
+        params = {"board": 19, "filters_per_layer": 128, "layers": 20, "filter_width_1": 5,
+                  "dense": 256, "dense_activation": "relu"}
+        params.update(kwargs)
+        if params.get("pass_logit"):
+            raise ValueError("ResnetPolicyValue has no pass logit")
+        layers, add, inp, path = ResnetPolicy._trunk(params)
+        return CNNPolicyValue._two_heads(layers, add, inp, path, params)

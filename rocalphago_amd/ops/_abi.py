@@ -43,6 +43,8 @@ SIGNATURES = {
     "rag_policy_head_dual": [P] * 15 + [I, I, I, I, I, F, P],
     "rag_head_bwd2": [P] * 12 + [I] * 5 + [P] * 5,
     "rag_head_bwd2_workspace": [I, I, I],
+    "rag_policy_head_dual_relu": [P] * 15 + [I, I, I, I, I, F, P],
+    "rag_head_bwd2_relu": [P] * 12 + [I] * 4 + [P] * 5,
     "rag_head_linear": [P, P, P, P, I, I, I, I, P],
     "rag_value_mlp_fwd": [P, P, P, P, P, P, P, P, I, I, I, I, P],
     "rag_value_mlp_workspace": [I, I],

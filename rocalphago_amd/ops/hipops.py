@@ -540,11 +540,14 @@ def policy_head_soft(h, w, b0, pbias, probs, K, targets, sweight=None, loss=None
 
 
 def policy_head_dual(h, w, b0, pbias, wv, b0v, probs, zv, K, labels=None, targets=None,
-                     sweight=None, loss=None, dz=None, hit=None, mode=0, gscale=1.0, dzsum=None):
+                     sweight=None, loss=None, dz=None, hit=None, mode=0, gscale=1.0, dzsum=None,
+                     relu_in=False):
     """Both heads of the policy-value network in one pass over ``h``: policy_head_fwd
     (``labels``, modes 0 / 1 / 2) or, with dense ``targets``, policy_head_soft (mode 1), without
     a pass logit, plus the value head's 1x1 conv ``zv`` [B, S*S] = h . wv + b0v (fp32) from the
-    same loaded channels (head.hip, the DUAL forms of the two policy-head kernels)."""
+    same loaded channels (head.hip, the DUAL forms of the two policy-head kernels).
+    ``relu_in``: ``h`` is a raw residual sum and the kernels clamp it at 0 in their loads (the
+    results of the plain form on ReLU(h), bit for bit)."""
     B, WP, _, KP = h.shape
     S = WP - 2
     S2 = S * S
@@ -559,7 +562,8 @@ def policy_head_dual(h, w, b0, pbias, wv, b0v, probs, zv, K, labels=None, target
             or wv is None or wv.numel() < K or w.numel() < K):
         raise ValueError("policy_head_dual: zv must be contiguous fp32 [%d, %d], w / wv [K]"
                          % (B, S2))
-    _check(_lib().rag_policy_head_dual(
+    fn = _lib().rag_policy_head_dual_relu if relu_in else _lib().rag_policy_head_dual
+    _check(fn(
         _ptr(h), _ptr(w), _ptr(b0), _ptr(pbias), _ptr(wv), _ptr(b0v), _ptr(probs), _ptr(zv),
         _ptr(labels), _ptr(targets), _ptr(sweight), _ptr(loss), _ptr(dz), _ptr(hit),
         _ptr(dzsum), B, S, KP, K, mode, float(gscale), _stream()), "policy_head_dual")
@@ -608,11 +612,15 @@ _head2_ws = {}
 
 
 def head_bwd2(h, wp, wv, dzp, dzv, dh, dwp, dwv, db0p, db0v, dpbias, K, relu_mask=True,
-              work=None, metrics=None, dzsum=None):
+              work=None, metrics=None, dzsum=None, relu_in=False):
     """head_bwd for two 1x1 heads on one trunk output (policy wp / dzp, value wv / dzv): dH =
     (dzp wp + dzv wv), ReLU-masked, written once; dwp, dwv, dpbias = sum_b dzp, db0p (from
     ``dzsum`` when given, else from dzp), db0v = sum dzv. All overwritten, not accumulated;
-    ``metrics`` as head_bwd. h is read once."""
+    ``metrics`` as head_bwd. h is read once. ``relu_in``: ``h`` is a raw residual sum; the
+    weight gradients sum over max(h, 0) and the mask h > 0 always applies (``relu_mask`` must
+    be true)."""
+    if relu_in and not relu_mask:
+        raise ValueError("head_bwd2: relu_in implies the ReLU mask")
     B, WP, _, KP = h.shape
     S = WP - 2
     for t in (dzp, dzv):
@@ -637,10 +645,13 @@ def head_bwd2(h, wp, wv, dzp, dzv, dh, dwp, dwv, db0p, db0v, dpbias, K, relu_mas
             raise ValueError("head_bwd2 metrics: loss [B], hit [B], fp32 acc [2]")
     if dzsum is not None and dzsum.numel() < B:
         raise ValueError("head_bwd2 dzsum: [B] per-board sums expected")
-    _check(_lib().rag_head_bwd2(_ptr(h), _ptr(wp), _ptr(wv), _ptr(dzp), _ptr(dzv), _ptr(dh),
-                                _ptr(dwp), _ptr(dwv), _ptr(db0p), _ptr(db0v), _ptr(dpbias),
-                                _ptr(work), B, S, KP, K, int(relu_mask), _ptr(ml), _ptr(mh),
-                                _ptr(acc), _ptr(dzsum), _stream()), "head_bwd2")
+    head = (_ptr(h), _ptr(wp), _ptr(wv), _ptr(dzp), _ptr(dzv), _ptr(dh), _ptr(dwp), _ptr(dwv),
+            _ptr(db0p), _ptr(db0v), _ptr(dpbias), _ptr(work), B, S, KP, K)
+    tail = (_ptr(ml), _ptr(mh), _ptr(acc), _ptr(dzsum), _stream())
+    if relu_in:
+        _check(_lib().rag_head_bwd2_relu(*(head + tail)), "head_bwd2")
+    else:
+        _check(_lib().rag_head_bwd2(*(head + (int(relu_mask),) + tail)), "head_bwd2")
 
 
 def head_linear(h, w, b0, z, K):

@@ -116,7 +116,8 @@ def run(cmd_line_args=None):
     parser.add_argument("--size", type=int, default=19, help="Board size. Default: 19")
     parser.add_argument("--value", default=None,
                         help="Path to a value model JSON (default: rollouts only; omit it with "
-                             "a CNNPolicyValue policy, whose own value head is searched with)")
+                             "a policy-value network as policy, whose own value head is searched "
+                             "with)")
     parser.add_argument("--seed", type=int, default=0, help="Seed of the search and the sampling")
     parser.add_argument("--temperature-moves", type=int, default=0,
                         help="The first so many plies are drawn in proportion to the visit "
@@ -133,7 +134,7 @@ def run(cmd_line_args=None):
         raise ValueError("the policy plays %dx%d boards, --size is %d" %
                          (policy.model.input_shape[-1], policy.model.input_shape[-1], args.size))
     if isinstance(policy, CNNPolicyValue) and args.value:
-        raise ValueError("a CNNPolicyValue policy searches with its own value head: omit --value")
+        raise ValueError("a policy-value network searches with its own value head: omit --value")
     value = CNNValue.load_model(args.value) if args.value else None
     mcts = ParallelMCTS(policy, value, n_playout=args.playouts, seed=args.seed)
     n = generate_search_data(mcts, args.games, args.out_file, size=args.size,

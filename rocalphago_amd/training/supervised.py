@@ -253,10 +253,11 @@ NO_OUTCOMES = ("a policy-value network trains on a dataset with an 'outcomes' ar
 
 
 class PolicyValueTrainer(SupervisedTrainer):
-    """SupervisedTrainer for a CNNPolicyValue: the policy head on the dataset's moves or visit
-    distributions as before, the value head under ``value_weight`` * MSE on the dataset's
-    ``outcomes`` (invariant under the board symmetries). On the GPU one fused step
-    (fused.DualPlan.fwd_bwd); without a plan (CPU, fp32) ``train_on_batch(X, [Yp, Yv])``.
+    """SupervisedTrainer for a policy-value network (CNNPolicyValue, ResnetPolicyValue): the
+    policy head on the dataset's moves or visit distributions as before, the value head under
+    ``value_weight`` * MSE on the dataset's ``outcomes`` (invariant under the board
+    symmetries). On the GPU one fused step (fused.DualPlan.fwd_bwd, which ResnetDualPlan
+    inherits); without a plan (CPU, fp32) ``train_on_batch(X, [Yp, Yv])``.
     ``pop_metrics`` / ``evaluate`` return (policy loss, accuracy, value loss), the value loss
     unweighted: mean((v - outcome)^2)."""
 
@@ -405,7 +406,7 @@ def run_training(cmd_line_args=None):
     parser.add_argument("--symmetries", help="Comma-separated list of transforms, subset of noop,rot90,rot180,rot270,fliplr,flipud,diag1,diag2", default='noop,rot90,rot180,rot270,fliplr,flipud,diag1,diag2')  # noqa: E501
     parser.add_argument("--seed", help="RNG seed for shuffling / symmetries", type=int, default=None)  # noqa: E501
     parser.add_argument("--targets", help="Policy targets: actions (the move played, one-hot) or visits (the dataset's search visit counts, normalised; training/search_data.py writes them). Default: actions", choices=["actions", "visits"], default="actions")  # noqa: E501
-    parser.add_argument("--value-weight", help="Weight of the value head's MSE term in the loss of a policy-value network (CNNPolicyValue; its dataset needs 'outcomes'). An error for other models. Default: 1.0", type=float, default=None)  # noqa: E501
+    parser.add_argument("--value-weight", help="Weight of the value head's MSE term in the loss of a policy-value network (CNNPolicyValue or ResnetPolicyValue; its dataset needs 'outcomes'). An error for other models. Default: 1.0", type=float, default=None)  # noqa: E501
     parser.add_argument("--dtype", help="GPU compute precision: bf16 (fused HIP kernels) or fp32 (reference precision, generic executor). Default: bf16", choices=["bf16", "fp32"], default="bf16")  # noqa: E501
     if cmd_line_args is None:
         args = parser.parse_args()
@@ -429,7 +430,8 @@ def run_training(cmd_line_args=None):
     model = policy.model
     dual = isinstance(policy, CNNPolicyValue)
     if args.value_weight is not None and not dual:
-        raise ValueError("--value-weight needs a policy-value network (CNNPolicyValue), %s is a "
+        raise ValueError("--value-weight needs a policy-value network (CNNPolicyValue or "
+                         "ResnetPolicyValue), %s is a "
                          "%s" % (args.model, type(policy).__name__))
     value_weight = 1.0 if args.value_weight is None else args.value_weight
     if not dual:
