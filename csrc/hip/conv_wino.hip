@@ -28,11 +28,12 @@
 //     220 issue cycles per 1 KB piece (s_memtime segments) for 12 KB per 144 MFMAs, more than
 //     the MFMAs themselves;
 //   * V slab per chunk-phase, [2 sets][vrow = (board row) x 10 + t][32 ch] in LDS, double
-//     buffered (56 KB): built one chunk-phase ahead by every thread from raw input rows loaded
-//     straight from L2 into registers (two units per thread, loads one step ahead of their
-//     +- and 16-byte LDS stores). A fragment of 16 consecutive output pairs reads 16
-//     consecutive V rows (no halo columns in between, unlike the direct kernel's pixel slab):
-//     the row-bit-2 swizzle keeps it conflict-free;
+//     buffered (2 x 28 KB, 32 KB apart): built one chunk-phase ahead by every thread from raw
+//     input rows loaded straight from L2 into registers (two units per thread, one in a
+//     half-board block, loads one step ahead of their +- and 16-byte LDS stores; every address
+//     they and the fragment reads need is computed once per block, wino_geom). A fragment of
+//     16 consecutive output pairs reads 16 consecutive V rows (no halo columns in between,
+//     unlike the direct kernel's pixel slab): the row-bit-2 swizzle keeps it conflict-free;
 //   * one barrier per chunk-phase (the V buffer flip); no per-step barriers, the two waves of
 //     a SIMD overlap freely.
 #include <atomic>
@@ -51,7 +52,11 @@ constexpr int kWP = 192;                 // output pairs per block (a 19x19 boar
 constexpr int kVRows = 224;              // V slab rows (a 19x19 board: 21 x 10 = 210)
 constexpr int kRRows = 512;              // raw rows a block may touch (19x19: 21 x 21 + 1)
 constexpr int kVSlot = kVRows * kWK;
-constexpr int kLoopLds = 4 * kVSlot;     // [2 chunk-phase buffers][2 sets]
+// [2 chunk-phase buffers][2 sets]; the second buffer starts kVFlip bytes after the first, one
+// address bit, so a thread flips its precomputed V addresses with one XOR per chunk-phase
+constexpr int kVFlip = 32768;
+constexpr int kLoopLds = kVFlip / 2 + 2 * kVSlot;
+static_assert(2 * kVSlot * 2 <= kVFlip, "V ring: a buffer below the flip bit");
 constexpr int kRedU = 14;                // chunk loads in flight per reduce thread
 
 // Output-tile geometry per block width WN (output channels per block): 8 waves = MW wave rows
@@ -106,8 +111,23 @@ __device__ __forceinline__ bf16x8 vaddsub(const bf16x8& a, const bf16x8& b) {
   }
   return __builtin_bit_cast(bf16x8, o);
 }
-__device__ __forceinline__ bf16x8 vsum(const bf16x8& a, const bf16x8& b) { return vaddsub<1>(a, b); }
 __device__ __forceinline__ bf16x8 vdiff(const bf16x8& a, const bf16x8& b) { return vaddsub<-1>(a, b); }
+// (a + b, b - a) of 8 bf16, each rounded once, from one unpack of a and b: the two phase-1 sets
+// of a transform unit (V1 = d1 + d2, V2 = d2 - d1)
+__device__ __forceinline__ void vsumdiff(const bf16x8& a, const bf16x8& b, bf16x8& s, bf16x8& d) {
+  const u32x4 ua = __builtin_bit_cast(u32x4, a), ub = __builtin_bit_cast(u32x4, b);
+  u32x4 os, od;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    const float a0 = __uint_as_float(ua[w] << 16), a1 = __uint_as_float(ua[w] & 0xffff0000u);
+    const float b0 = __uint_as_float(ub[w] << 16), b1 = __uint_as_float(ub[w] & 0xffff0000u);
+    const bf16x2 rs = {(bf16)(a0 + b0), (bf16)(a1 + b1)}, rd = {(bf16)(b0 - a0), (bf16)(b1 - a1)};
+    os[w] = __builtin_bit_cast(uint32_t, rs);
+    od[w] = __builtin_bit_cast(uint32_t, rd);
+  }
+  s = __builtin_bit_cast(bf16x8, os);
+  d = __builtin_bit_cast(bf16x8, od);
+}
 // The same with the BN prologue (ResnetPolicy): the raw values are BN inputs x and
 // the transform runs on U = ReLU(cx x + cc) of each column (cx = cc = 0 on halo pixels: U = 0),
 // kept in fp32 up to the one rounding of V
@@ -126,6 +146,25 @@ __device__ __forceinline__ bf16x8 vaddsub_bn(const bf16x8& a, const bf16x8& b, f
     o[w] = __builtin_bit_cast(uint32_t, r);
   }
   return __builtin_bit_cast(bf16x8, o);
+}
+
+// vsumdiff with the BN prologue: ReLU(cx x + cc) once per raw value
+__device__ __forceinline__ void vsumdiff_bn(const bf16x8& a, const bf16x8& b, float cxa, float cca,
+                                            float cxb, float ccb, bf16x8& s, bf16x8& d) {
+  const u32x4 ua = __builtin_bit_cast(u32x4, a), ub = __builtin_bit_cast(u32x4, b);
+  u32x4 os, od;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    const float a0 = fmaxf(fmaf(cxa, __uint_as_float(ua[w] << 16), cca), 0.f);
+    const float a1 = fmaxf(fmaf(cxa, __uint_as_float(ua[w] & 0xffff0000u), cca), 0.f);
+    const float b0 = fmaxf(fmaf(cxb, __uint_as_float(ub[w] << 16), ccb), 0.f);
+    const float b1 = fmaxf(fmaf(cxb, __uint_as_float(ub[w] & 0xffff0000u), ccb), 0.f);
+    const bf16x2 rs = {(bf16)(a0 + b0), (bf16)(a1 + b1)}, rd = {(bf16)(b0 - a0), (bf16)(b1 - a1)};
+    os[w] = __builtin_bit_cast(uint32_t, rs);
+    od[w] = __builtin_bit_cast(uint32_t, rd);
+  }
+  s = __builtin_bit_cast(bf16x8, os);
+  d = __builtin_bit_cast(bf16x8, od);
 }
 
 // Fused BatchNorm of the 128-channel residual trunk (BNM template argument of conv_wino_kernel):
@@ -161,6 +200,13 @@ template <bool SINGLE, int MT> struct WinoGeom {
   int vb[SINGLE ? 1 : MT];  // V rows of this lane's output pairs (tap ky adds ky * TJ)
   uint32_t uoff;            // byte offset of this lane's 8 elements in its wave's first fragment
   int tu0, tu1;             // transform units of this thread (packed, see wino_geom)
+  // What the K loop needs of them, computed once per block (the loop paid ~137 VALU per 108
+  // MFMAs to decode and re-derive these every chunk-phase):
+  uint32_t ru[2];  // unit u: byte offset of its d0 in the block's raw rows (no unit: 0, a valid row)
+  int su[2];       // unit u: byte offset of its 16-byte V store in a set's slab, swizzle applied
+                   // (no unit: the last V row, read by nobody); wino_layer flips the buffer bit
+  int rv[3];       // SINGLE: byte offset of this lane's first V fragment read of tap row ky; the
+                   // set, the read group and the fragment are immediate offsets on top
 };
 
 // global loads are buffer loads: a wave-uniform descriptor (SGPRs), a 32-bit lane offset
@@ -198,7 +244,7 @@ __device__ __forceinline__ uint32_t wino_warm(const R& urs, int NOUT, int KIN) {
 
 template <int WN, bool SINGLE, int PAIRS>
 __device__ __forceinline__ WinoGeom<SINGLE, WinoTile<WN, PAIRS>::MT> wino_geom(int B, int S,
-                                                                              int nb) {
+                                                                              int nb, int KIN) {
   using T = WinoTile<WN, PAIRS>;
   constexpr int kWMT = T::MT;
   constexpr bool HALF = PAIRS == kHalfPairs;  // two blocks per board (SINGLE geometry)
@@ -244,8 +290,10 @@ __device__ __forceinline__ WinoGeom<SINGLE, WinoTile<WN, PAIRS>::MT> wino_geom(i
   // ---- transform units of this thread (the same for every chunk-phase): V row, 8-channel
   // group, raw row of d0 (named scalars: a runtime-indexed array went to scratch)
   // packed: V row (bits 0-9), 8-channel group (10-11), raw row of d0 (12-30), -1 = no unit
-  // (HALF: the V rows of padded rows i0 .. (last pair's row) + 2 only)
-  const int NU = HALF ? ((p0 + kHalfPairs - 1) / TJ - i0 + 3) * TJ * 4 : nb * VPB * 4;
+  // (HALF: the V rows of padded rows i0 .. (last real pair's row) + 2 only: at most 512 units,
+  // one per thread, wino_half_units)
+  const int pe = p0 + kHalfPairs < PB ? p0 + kHalfPairs : PB;
+  const int NU = HALF ? ((pe - 1) / TJ - i0 + 3) * TJ * 4 : nb * VPB * 4;
   auto unit = [&](int it) {
     const int u = threadIdx.x + it * 512;
     const int v = u >> 2;
@@ -255,7 +303,20 @@ __device__ __forceinline__ WinoGeom<SINGLE, WinoTile<WN, PAIRS>::MT> wino_geom(i
     return u < NU ? (v | ((u & 3) << 10) | (rr << 12)) : -1;
   };
   g.tu0 = unit(0);
-  g.tu1 = unit(1);
+  g.tu1 = HALF ? -1 : unit(1);
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int pk = u ? g.tu1 : g.tu0;
+    const int v = pk < 0 ? kVRows - 1 : (pk & 1023);
+    const int k8 = pk < 0 ? 0 : (pk >> 10) & 3, rr = pk < 0 ? 0 : pk >> 12;
+    g.ru[u] = (uint32_t)(rr * KIN + k8 * 8) * 2u;
+    g.su[u] = (v * kWK + ((k8 ^ swz4w(v)) * 8)) * 2;
+  }
+#pragma unroll
+  for (int ky = 0; ky < 3; ++ky) {
+    const int r = g.vb[0] + ky * TJ;  // rows r + 16 i and r + 48 share row bit 2
+    g.rv[ky] = (r * kWK + ((g.fq ^ swz4w(r)) * 8)) * 2;
+  }
   return g;
 }
 
@@ -270,13 +331,14 @@ __device__ __forceinline__ WinoGeom<SINGLE, WinoTile<WN, PAIRS>::MT> wino_geom(i
 // instantiation went from 244 VGPRs to 256 and 20 bytes of scratch, nothing else changed.
 template <int WN, bool SINGLE, int PAIRS, int BNM, bool CHAIN, typename R>
 __device__ __forceinline__ void wino_layer(
-    const R& urs, bf16* lds, const WinoGeom<SINGLE, WinoTile<WN, PAIRS>::MT>& g,
+    const R& urs, bf16* lds, WinoGeom<SINGLE, WinoTile<WN, PAIRS>::MT>& g,
     const bf16* __restrict__ X, const float* __restrict__ bias, bf16* __restrict__ Y,
     const bf16* __restrict__ mask, int B, int S, int KIN, int NOUT, int HO, int YC, int relu,
     int HM, int nb, const WinoBN& bn, const bf16* Unext) {
   using T = WinoTile<WN, PAIRS>;
   constexpr int kWMT = T::MT, kWNT = T::NT, kWN = WN, kEpRow = T::EpRow;
   constexpr bool HALF = PAIRS == kHalfPairs;
+  constexpr int kUnits = HALF ? 1 : 2;  // transform units per thread (wino_half_units)
   static_assert(BNM == 0 || (SINGLE && !HALF && WN == 128), "fused BN: the 128-wide one-board tile");
   static_assert(!CHAIN || (BNM == 0 && !HALF), "chain: plain one- or multi-board blocks");
   float* sred = reinterpret_cast<float*>(lds + T::Lds);
@@ -285,10 +347,10 @@ __device__ __forceinline__ void wino_layer(
   const long total_rows = g.total_rows;
   const int tu0 = g.tu0, tu1 = g.tu1;
   const int cchunks = KIN / kWK;
-  const int NK = 2 * cchunks;  // chunk-phases
   int vb[SINGLE ? 1 : kWMT];
 #pragma unroll
   for (int i = 0; i < (SINGLE ? 1 : kWMT); ++i) vb[i] = g.vb[i];
+  int vpar = 0;  // multi-board blocks: the byte offset of the V buffer being read
 
   const int NF = NOUT / 16;
   const uint32_t uoff = g.uoff;
@@ -319,10 +381,11 @@ __device__ __forceinline__ void wino_layer(
   }
   // raw rows of this block's boards (out of range, i.e. the last block's +1 row, reads 0)
   const auto xrs = wino_rsrc(X + (long)b0 * RPB * KIN, (total_rows - (long)b0 * RPB) * KIN * 2);
-  // The transform of V(kk) runs as four "ops" per thread and chunk-phase, two raw-pixel loads
-  // each: op 2u + h of unit u (h = set): phase 1 loads (d1, d2) for both sets (V1 = d1 + d2,
-  // V2 = d2 - d1), phase 2 (d0, d2) for set A (V0 = d0 - d2) and (d3, d1) for set B
-  // (V3' = d3 - d1). An op's loads go out one MFMA block before its +- and store.
+  // The transform of V(kk) runs as "ops" of two raw-pixel loads each. Phase 1: one op per unit,
+  // (d1, d2) loaded and unpacked once for both sets (V1 = d1 + d2, V2 = d2 - d1, two LDS
+  // stores). Phase 2: two ops per unit, (d0, d2) for set A (V0 = d0 - d2) and (d3, d1) for set
+  // B (V3' = d3 - d1). A one-board or multi-board thread owns two units, a half-board thread
+  // one (kUnits).
   // Every global load in the loop is issued unconditionally (a missing unit or a chunk-phase
   // past the end loads a valid dummy row and skips only its LDS store): with loads under
   // branches hipcc's counter analysis fell back to `s_waitcnt vmcnt(0)`, so each transform
@@ -332,27 +395,33 @@ __device__ __forceinline__ void wino_layer(
   // before its +- and store, ~0.5 us: the raw rows of a layer written by the previous launch
   // come from HBM / MALL, and one block's distance cost up to 7 us per launch in the step
   bf16x8 da0, db0, da1, db1;
-  auto op_unit = [&](int o, int& v, int& k8, int& rr) {
-    int pk = (o >> 1) ? tu1 : tu0;
-    asm volatile("" : "+v"(pk));
-    v = pk < 0 ? -1 : (pk & 1023);
-    pk = pk < 0 ? 0 : pk;
-    k8 = (pk >> 10) & 3;
-    rr = pk >> 12;
-  };
+  // Op numbering. Phase 1 (P1): op u = unit u, one load pair (d1, d2) for both sets, kept in
+  // register pair u. Phase 2: op 2u + h of unit u, set h, in register pair h. The addresses are
+  // wino_geom's: the raw offset of d0 in a VGPR, the pixel (d_s: s KIN elements on) and the
+  // chunk in the load's scalar offset, the set in the store's immediate offset.
   // P1: the V being built belongs to phase 1 (compile time: a runtime phase test put both
   // arithmetic paths and a join into the loop, and hipcc's counters and registers with them)
-  auto op_load = [&](auto p1c, int kk, auto oc) {  // kk may be NK (past the end): a dummy
+  auto op_load = [&](auto p1c, int c, auto oc) {  // c: the chunk (past the end: a dummy's)
     constexpr bool P1 = decltype(p1c)::value;
-    constexpr int o = decltype(oc)::value, h = o & 1;
-    int v, k8, rr;
-    op_unit(o, v, k8, rr);
-    const int ra = P1 ? 1 : (h ? 3 : 0), rb = P1 ? 2 : (h ? 1 : 2);
-    const int so = (kk % cchunks) * kWK * 2;
-    const uint32_t o0 = (uint32_t)((rr + ra) * KIN + k8 * 8) * 2u;
-    const uint32_t o1 = (uint32_t)((rr + rb) * KIN + k8 * 8) * 2u;
-    const bf16x8 a = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(xrs, o0, so, 0));
-    const bf16x8 b = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(xrs, o1, so, 0));
+    constexpr int o = decltype(oc)::value, u = P1 ? o : o >> 1, h = P1 ? o : o & 1;
+    constexpr int ra = P1 ? 1 : (h ? 3 : 0), rb = P1 ? 2 : (h ? 1 : 2);
+    const int so = c * kWK * 2;
+    // Nothing here relies on the descriptor's range check covering the scalar offset. d1 and d2 of
+    // a unit lie in range whenever its d0 does (d0 is at most padded column S - 1), so their
+    // pixel may ride in the scalar offset; d3 of the last board's last unit (odd S) is the raw
+    // row past the end, which must read 0 and not memory: its pixel goes into the lane offset.
+    // (added here, not hoisted into two more persistent registers: one VALU add, or none where
+    // KIN is a compile-time constant and the sum folds into the load's immediate offset)
+    uint32_t roa = g.ru[u];
+    if constexpr (ra == 3) {
+      asm volatile("" : "+v"(roa));
+      roa += 3u * (uint32_t)KIN * 2u;
+    }
+    const int soa = so + (ra == 3 ? 0 : ra * KIN * 2);
+    const bf16x8 a = __builtin_bit_cast(
+        bf16x8, __builtin_amdgcn_raw_buffer_load_b128(xrs, roa, soa, 0));
+    const bf16x8 b = __builtin_bit_cast(
+        bf16x8, __builtin_amdgcn_raw_buffer_load_b128(xrs, g.ru[u], so + rb * KIN * 2, 0));
     if constexpr (h) {
       da1 = a;
       db1 = b;
@@ -361,25 +430,42 @@ __device__ __forceinline__ void wino_layer(
       db0 = b;
     }
   };
-  auto op_store = [&](auto p1c, int kk, auto oc) {  // branch-free: no unit -> the last V row
+  auto op_store = [&](auto p1c, auto oc) {  // branch-free: no unit -> the last V row
     constexpr bool P1 = decltype(p1c)::value;
-    constexpr int o = decltype(oc)::value, h = o & 1;
-    int v, k8, rr;
-    op_unit(o, v, k8, rr);
-    v = v < 0 ? kVRows - 1 : v;
-    bf16* vs = lds + (kk & 1) * 2 * kVSlot + h * kVSlot;
+    constexpr int o = decltype(oc)::value, u = P1 ? o : o >> 1, h = P1 ? o : o & 1;
+    constexpr int ra = P1 ? 1 : (h ? 3 : 0), rb = P1 ? 2 : (h ? 1 : 2);
+    char* vs = reinterpret_cast<char*>(lds) + g.su[u];
     const bf16x8 da = h ? da1 : da0, db = h ? db1 : db0;
-    bf16x8 val;
-    if constexpr (BNM == 1) {
-      constexpr int q = o >> 1, ra = P1 ? 1 : (h ? 3 : 0), rb = P1 ? 2 : (h ? 1 : 2);
-      if constexpr (P1 && h)
-        val = vaddsub_bn<-1>(db, da, bcx[q][rb], bcc[q][rb], bcx[q][ra], bcc[q][ra]);
+    if constexpr (P1) {  // V1 = d1 + d2 (set A), V2 = d2 - d1 (set B) from one unpack
+      bf16x8 vs1, vs2;
+      if constexpr (BNM == 1)
+        vsumdiff_bn(da, db, bcx[u][ra], bcc[u][ra], bcx[u][rb], bcc[u][rb], vs1, vs2);
       else
-        val = vaddsub_bn<P1 ? 1 : -1>(da, db, bcx[q][ra], bcc[q][ra], bcx[q][rb], bcc[q][rb]);
+        vsumdiff(da, db, vs1, vs2);
+      *reinterpret_cast<bf16x8*>(vs) = vs1;
+      *reinterpret_cast<bf16x8*>(vs + kVSlot * 2) = vs2;
     } else {
-      val = P1 ? (h ? vdiff(db, da) : vsum(da, db)) : vdiff(da, db);
+      bf16x8 val;
+      if constexpr (BNM == 1)
+        val = vaddsub_bn<-1>(da, db, bcx[u][ra], bcc[u][ra], bcx[u][rb], bcc[u][rb]);
+      else
+        val = vdiff(da, db);
+      *reinterpret_cast<bf16x8*>(vs + h * kVSlot * 2) = val;
     }
-    *reinterpret_cast<bf16x8*>(vs + v * kWK + ((k8 ^ swz4w(v)) * 8)) = val;
+  };
+  // the V stores go to the buffer the MFMAs do not read, the reads to the other one: both flip
+  // at the barrier of every chunk-phase (one XOR per address)
+  auto flip_su = [&]() {
+#pragma unroll
+    for (int u = 0; u < kUnits; ++u) g.su[u] ^= kVFlip;
+  };
+  auto flip_rv = [&]() {
+    if constexpr (SINGLE) {
+#pragma unroll
+      for (int ky = 0; ky < 3; ++ky) g.rv[ky] ^= kVFlip;
+    } else {
+      vpar ^= kVFlip;
+    }
   };
 
   f32x4 accA[kWNT][kWMT], accB[kWNT][kWMT];
@@ -394,22 +480,23 @@ __device__ __forceinline__ void wino_layer(
   // live, hipcc spilled the transform's raw loads and waited for them at once)
   constexpr int kH = kWMT / T::RG;  // V fragments per read group
   bf16x8 xa[kH], wA[kWNT], wB[kWNT];
-  auto read_v = [&](int kk, int ky, int set, int h) {
-    const bf16* vs = lds + ((kk & 1) * 2 + set) * kVSlot;
-    const int sh = ky * TJ;
+  auto read_v = [&](int ky, int set, int h) {
     if constexpr (SINGLE) {
-      int r0 = vb[0];
-      asm volatile("" : "+v"(r0));  // not hoisted: per-(fragment, ky) addresses, 18 registers
-      r0 += sh + h * kH * 16;
-      const int sw0 = (fq ^ swz4w(r0)) * 8;  // rows r0 + 16 i share row bit 2
+      // one address per tap row (wino_geom); the set, the read group (+48 rows) and the
+      // fragment (+16 rows) keep row bit 2: immediate offsets of the ds_read
+      const char* vs = reinterpret_cast<const char*>(lds) + g.rv[ky];
 #pragma unroll
       for (int i = 0; i < kH; ++i)
-        xa[i] = *reinterpret_cast<const bf16x8*>(vs + (r0 + i * 16) * kWK + sw0);
+        xa[i] = *reinterpret_cast<const bf16x8*>(
+            vs + (set * kVSlot + (h * kH + i) * 16 * kWK) * 2);
     } else {
+      const bf16* vs = reinterpret_cast<const bf16*>(reinterpret_cast<const char*>(lds) + vpar) +
+                       set * kVSlot;
+      const int sh = ky * TJ;
 #pragma unroll
       for (int i = 0; i < kH; ++i) {
         int v = vb[h * kH + i];
-        asm volatile("" : "+v"(v));
+        asm volatile("" : "+v"(v));  // not hoisted: per-(fragment, ky) addresses, 18 registers
         const int r = v + sh;
         xa[i] = *reinterpret_cast<const bf16x8*>(vs + r * kWK + ((fq ^ swz4w(r)) * 8));
       }
@@ -426,47 +513,53 @@ __device__ __forceinline__ void wino_layer(
     wB[j] = wfrag(2, 0, j);
   }
   op_load(IntC<1>{}, 0, IntC<0>{});  // V(0) (phase 1)
-  op_store(IntC<1>{}, 0, IntC<0>{});
-  op_load(IntC<1>{}, 0, IntC<1>{});
-  op_store(IntC<1>{}, 0, IntC<1>{});
-  op_load(IntC<1>{}, 0, IntC<2>{});
-  op_store(IntC<1>{}, 0, IntC<2>{});
-  op_load(IntC<1>{}, 0, IntC<3>{});
-  op_store(IntC<1>{}, 0, IntC<3>{});
+  op_store(IntC<1>{}, IntC<0>{});
+  if constexpr (kUnits == 2) {
+    op_load(IntC<1>{}, 0, IntC<1>{});
+    op_store(IntC<1>{}, IntC<1>{});
+  }
+  flip_su();
   if constexpr (!CHAIN) asm volatile("" ::"v"(warm));  // (the warming loads are not dead)
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
 
-  // one chunk-phase: CUR = phase of kk (its taps), NXT = phase of kk + 1 (the V built and the
-  // weights prefetched during kk)
-  auto chunk_phase = [&](int kk, auto curc, auto nxtc) {
+  // The transform ops of the V being built, in the six (ky, set) slots of a chunk-phase: a
+  // slot first stores the op loaded two slots earlier, then loads its own (loads in slots
+  // 0..3, stores in 2..5; in the last chunk-phase they fill the idle buffer, read by nobody).
+  // Phase 1 has one op per unit (slots 0, 1 load, 2, 3 store), phase 2 two.
+  auto slot_store = [&](auto nxtc, auto tc) {
+    constexpr bool NXT1 = decltype(nxtc)::value;
+    constexpr int o = decltype(tc)::value - 2;
+    if constexpr (o >= 0 && o < (NXT1 ? 1 : 2) * kUnits) op_store(nxtc, IntC<o>{});
+  };
+  auto slot_load = [&](auto nxtc, int cn, auto tc) {
+    constexpr bool NXT1 = decltype(nxtc)::value;
+    constexpr int o = decltype(tc)::value;
+    if constexpr (o < (NXT1 ? 1 : 2) * kUnits) op_load(nxtc, cn, IntC<o>{});
+  };
+
+  // one chunk-phase of chunk c: CUR = its phase (its taps), NXT = the phase of the next one
+  // (the V built and the weights prefetched meanwhile), cn = the next one's chunk; `last`: none
+  // follows (cn: any valid chunk)
+  auto chunk_phase = [&](int c, int cn, bool last, auto curc, auto nxtc) {
     constexpr bool CUR1 = decltype(curc)::value, NXT1 = decltype(nxtc)::value;
-#pragma unroll
-    for (int ky = 0; ky < 3; ++ky) {
-      // next step's weights: (kk, ky + 1) or (kk + 1, 0); past the end: a dummy (the last
-      // step's again)
+    auto step = [&](auto kyc) {
+      constexpr int ky = decltype(kyc)::value;
+      // next step's weights: (ky + 1) of this chunk-phase or row 0 of the next; past the end:
+      // a dummy (the last step's again)
       const bool nxt1 = ky < 2 ? CUR1 : NXT1;
-      int nkk = ky < 2 ? kk : kk + 1, nky = ky < 2 ? ky + 1 : 0;
-      if (nkk >= NK) {
-        nkk = NK - 1;
-        nky = 2;
-      }
-      const int nc = nkk % cchunks;
+      const int nc = ky < 2 || last ? c : cn;
+      const int nky = ky < 2 ? ky + 1 : (last ? 2 : 0);
       const int ntA = nky * 4 + (nxt1 ? 1 : 0), ntB = nky * 4 + (nxt1 ? 2 : 3);
-      // transform ops of V(kk + 1) in the six (ky, set) slots: slot t stores op t-2 and loads
-      // op t (loads in slots 0..3, stores in 2..5; in the last chunk-phase they fill the idle
-      // buffer, read by nobody)
-      if (ky == 1) op_store(nxtc, kk + 1, IntC<0>{});
-      if (ky == 2) op_store(nxtc, kk + 1, IntC<2>{});
+      slot_store(nxtc, IntC<2 * ky>{});
       __builtin_amdgcn_sched_barrier(0);
-      if (ky == 0) op_load(nxtc, kk + 1, IntC<0>{});
-      if (ky == 1) op_load(nxtc, kk + 1, IntC<2>{});
+      slot_load(nxtc, cn, IntC<2 * ky>{});
       __builtin_amdgcn_sched_barrier(0);
       // ---- set A
 #pragma unroll
       for (int h = 0; h < T::RG; ++h) {
-        read_v(kk, ky, 0, h);
+        read_v(ky, 0, h);
 #pragma unroll
         for (int j = 0; j < kWNT; ++j) {
 #pragma unroll
@@ -478,16 +571,14 @@ __device__ __forceinline__ void wino_layer(
       // (scheduling fences: hipcc otherwise reads set B's fragments into a second register set
       // while set A's MFMAs still hold the first, and the kernel spills)
       __builtin_amdgcn_sched_barrier(0);
-      if (ky == 1) op_store(nxtc, kk + 1, IntC<1>{});
-      if (ky == 2) op_store(nxtc, kk + 1, IntC<3>{});
+      slot_store(nxtc, IntC<2 * ky + 1>{});
       __builtin_amdgcn_sched_barrier(0);  // the old op's registers free before the new loads
-      if (ky == 0) op_load(nxtc, kk + 1, IntC<1>{});
-      if (ky == 1) op_load(nxtc, kk + 1, IntC<3>{});
+      slot_load(nxtc, cn, IntC<2 * ky + 1>{});
       __builtin_amdgcn_sched_barrier(0);
       // ---- set B
 #pragma unroll
       for (int h = 0; h < T::RG; ++h) {
-        read_v(kk, ky, 1, h);
+        read_v(ky, 1, h);
 #pragma unroll
         for (int j = 0; j < kWNT; ++j) {
 #pragma unroll
@@ -497,16 +588,21 @@ __device__ __forceinline__ void wino_layer(
         }
       }
       __builtin_amdgcn_sched_barrier(0);
-    }
+    };
+    step(IntC<0>{});
+    step(IntC<1>{});
+    step(IntC<2>{});
     // V(kk + 1) complete and V(kk) read by every wave before the buffers flip
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
+    flip_su();
+    flip_rv();
   };
 
 #pragma unroll 1
-  for (int kk = 0; kk < cchunks - 1; ++kk) chunk_phase(kk, IntC<1>{}, IntC<1>{});
-  chunk_phase(cchunks - 1, IntC<1>{}, IntC<0>{});
+  for (int c = 0; c < cchunks - 1; ++c) chunk_phase(c, c + 1, false, IntC<1>{}, IntC<1>{});
+  chunk_phase(cchunks - 1, 0, false, IntC<1>{}, IntC<0>{});
   // (M1, M2) -> (M1 + M2, M1 - M2)
 #pragma unroll
   for (int j = 0; j < kWNT; ++j)
@@ -517,7 +613,9 @@ __device__ __forceinline__ void wino_layer(
       accB[j][i] = a - b;
     }
 #pragma unroll 1
-  for (int kk = cchunks; kk < NK; ++kk) chunk_phase(kk, IntC<0>{}, IntC<0>{});
+  for (int c = 0; c < cchunks; ++c)
+    chunk_phase(c, c + 1 < cchunks ? c + 1 : 0, c + 1 == cchunks, IntC<0>{}, IntC<0>{});
+  flip_su();  // as wino_geom left them (a chain's next layer): 2 cchunks + 2 flips
 
   // ---- epilogue: bias (+ ReLU) -> bf16 image [pair][column][channel] in LDS, then whole
   // 384-byte pixel rows out with the dgrad mask applied
@@ -654,7 +752,7 @@ conv_wino_kernel(const bf16* __restrict__ X, const bf16* __restrict__ U,
     if (bn.spart && threadIdx.x < 128) sred[threadIdx.x] = 0.f;  // published by the first barrier
   }
   const auto urs = wino_rsrc(U, 12L * NOUT * KIN * 2);
-  const auto g = wino_geom<WN, SINGLE, PAIRS>(B, S, nb);
+  auto g = wino_geom<WN, SINGLE, PAIRS>(B, S, nb, KIN);
   wino_layer<WN, SINGLE, PAIRS, BNM, false>(urs, lds, g, X, bias, Y, mask, B, S, KIN, NOUT, HO,
                                             YC, relu, HM, nb, bn, nullptr);
   // a deferred wgrad reduction riding in this launch (every block claims units of it)
@@ -684,7 +782,7 @@ __global__ void __launch_bounds__(512, 1)
 conv_wino_chain_kernel(WinoChain c, int B, int S, int nb) {
   using T = WinoTile<WN, kWP>;
   __shared__ __attribute__((aligned(16))) bf16 lds[T::Lds];
-  const auto g = wino_geom<WN, SINGLE, kWP>(B, S, nb);
+  auto g = wino_geom<WN, SINGLE, kWP>(B, S, nb, WN);
   // the first layer's weights towards L2 (every later layer's: during the layer before it)
   const uint32_t warm = wino_warm(wino_rsrc(c.U[0], 12L * WN * WN * 2), WN, WN);
   asm volatile("" ::"v"(warm));
@@ -789,9 +887,24 @@ RAG_API int rag_conv_wino_ok(int S, int HI, int KIN, int NOUT, int KS) {
 // on MI355X) against the direct kernel's per-pixel cost (57 us per 256 boards), so a ragged
 // last wave gives the gain back.
 // Half-board blocks (96 pairs, 192-wide tiles): boards of more than 96 and at most 192 pairs.
+// Transform units (V row x 8-channel group) of the larger of a board's two half-board blocks:
+// the V rows of the padded rows from its first pair's to its last real pair's + 2 (wino_geom).
+// A half-board block runs one unit per thread, so it takes boards of at most 512 units -- every
+// board that passes the other two conditions (14x14 .. 19x19: 448 .. 480).
+static int wino_half_units(int S) {
+  const int TJ = (S + 1) / 2, PB = S * TJ;
+  int most = 0;
+  for (int p0 = 0; p0 < PB; p0 += kHalfPairs) {
+    const int pe = p0 + kHalfPairs < PB ? p0 + kHalfPairs : PB;
+    const int n = ((pe - 1) / TJ - p0 / TJ + 3) * TJ * 4;
+    most = n > most ? n : most;
+  }
+  return most;
+}
 static bool wino_half_ok(int S, int NOUT) {
   const int TJ = (S + 1) / 2;
-  return NOUT % 192 == 0 && wino_boards_per_block(S) == 1 && S * TJ > kHalfPairs;
+  return NOUT % 192 == 0 && wino_boards_per_block(S) == 1 && S * TJ > kHalfPairs &&
+         wino_half_units(S) <= 512;
 }
 // CUs of the device, kept once a device answered (no device visible: 0, and asked again).
 static int wino_cus() {
@@ -838,7 +951,7 @@ RAG_API int rag_conv_wino_mode(int B, int S, int KIN, int NOUT) {
 // half (192-wide tiles only): run half-board blocks whenever the shape has them (wino_half_ok),
 // not only when the one-board grid would leave a ragged wave -- for launches that share the chip
 // with long resident kernels (the search's GPU rollouts hold a 128-VGPR wave on most CUs: a
-// one-board block needs 2 x 244 VGPRs on every SIMD, a half-board block 2 x 165).
+// one-board block needs 2 x 248 VGPRs on every SIMD, a half-board block 2 x 165).
 int rag_conv_wino_launch(const void* X, const void* W, const float* bias, void* Y,
                          const void* mask, int B, int S, int KIN, int NOUT, int HO, int YC,
                          int relu, int HM, hipStream_t stream, const WgradRed* red, int half) {
