@@ -3,6 +3,7 @@ step, the raw-top head kernels next to the ReLU pass they fold in, and the searc
 
   python benchmarks/resdual_bench.py [--batch 256] [--filters 128] [--layers 20] [--steps 100]
                                      [--playouts 8192] [--moves 6] [--skip-search]
+                                     [--bn-axis {-1,1}]
 
 One JSON line:
   * resdual_step_positions_per_s: PolicyValueTrainer.step (visit targets + outcomes, 49 planes)
@@ -14,6 +15,15 @@ One JSON line:
     head_bwd2 (the pass is charged to the forward in the plan; here each pair carries it, so
     the two rows bracket its cost). The candidates alternate in the same process
     (dual_bench.alternate); ``spread`` is the largest max - min over a candidate's rounds;
+  * --bn-axis 1 builds the networks with channel BatchNormalization (one statistic per
+    channel; ResTrunk's unfused channel kernels). resdual_step_column_unfused_positions_per_s is
+    always the column network's step with ``bn_prologue = False`` and ``WINO_MODE = "0"``, the
+    launch-for-launch counterpart of the channel step, and with --bn-axis 1
+    resdual_step_column_fused_positions_per_s the column step as it ships (the distance a fused
+    channel kernel would have to close);
+  * bn_us: at B = 256, K = --filters, S = 19 the column and the channel form of the train-forward
+    statistics, the BN + ReLU apply, the backward coefficients and the backward apply with the
+    residual, each pair alternating in this process (``spread`` as above);
   * search_sims_per_s: ParallelMCTS(net, None) at mcts_bench.py --moves 6 --dual's geometry
     (8192 playouts, waves of 512, lambda 0.5, GPU rollouts, from the empty board).
 """
@@ -93,17 +103,63 @@ def head_kernels(B, K, dev):
     return {"fwd": fwd, "bwd": bwd}
 
 
-def sl_steps(B, filters, layers, steps, warmup, dev):
+def bn_kernels(K, dev, B=256, S=19):
+    """us per call of the four stand-alone BN kernels' column and channel forms on the same
+    activations (bn.hip rag_bn_* / rag_bn_ch_*)."""
+    KP = ops.pad_channels(K)
+    g = torch.Generator(device=dev)
+    g.manual_seed(2)
+    x, dy, res = (ops.pack_nchw(torch.randn(B, K, S, S, device=dev, generator=g), 1, KP)
+                  for _ in range(3))
+    out = ops.alloc_padded(B, S, 1, KP, dev)
+    forms = {}
+    for name, n, slots in (("column", S, S), ("channel", K, KP)):
+        gamma, rvar = torch.ones(n, device=dev), torch.ones(n, device=dev)
+        beta, rmean = torch.zeros(n, device=dev), torch.zeros(n, device=dev)
+        forms[name] = dict(gamma=gamma, beta=beta, rmean=rmean, rvar=rvar,
+                           dgamma=torch.empty(n, device=dev), dbeta=torch.empty(n, device=dev),
+                           stats=torch.zeros(2, slots, device=dev),
+                           coef=torch.zeros(3, slots, device=dev),
+                           bcoef=torch.zeros(3, slots, device=dev))
+
+    def train_fwd(fn, f):
+        return lambda: fn(x, B, S, K, f["gamma"], f["beta"], f["rmean"], f["rvar"], 1e-3, 0.99,
+                          f["stats"], f["coef"])
+
+    def bwd_coef(fn, f):
+        return lambda: fn(x, dy, B, S, K, f["gamma"], f["stats"], f["dgamma"], f["dbeta"],
+                          f["bcoef"])
+
+    def apply_relu(fn, f):
+        return lambda: fn(x, out, B, S, K, coef=f["coef"], relu=True)
+
+    def bwd_apply(fn, f):
+        return lambda: fn(x, out, B, S, K, coef=f["bcoef"], relu=False, dy=dy, residual=res)
+
+    col, ch = forms["column"], forms["channel"]
+    res_us = {}
+    for key, make, fcol, fch in (("train_fwd", train_fwd, ops.bn_train_fwd, ops.bn_ch_train_fwd),
+                                 ("apply_relu", apply_relu, ops.bn_apply, ops.bn_ch_apply),
+                                 ("bwd_coef", bwd_coef, ops.bn_bwd_coef, ops.bn_ch_bwd_coef),
+                                 ("bwd_apply_residual", bwd_apply, ops.bn_apply,
+                                  ops.bn_ch_apply)):
+        res_us[key] = alternate_with_spread({"column": make(fcol, col), "channel": make(fch, ch)})
+    return res_us
+
+
+def sl_steps(B, filters, layers, steps, warmup, dev, bn_axis=-1):
     from rocalphago_amd.features.preprocessing import DEFAULT_FEATURES, VALUE_FEATURES
     from rocalphago_amd.models import kerasish as K
+    from rocalphago_amd.models.engine import ResTrunk
     from rocalphago_amd.models.fused import ResnetDualPlan
     from rocalphago_amd.models.policy import ResnetPolicy
     from rocalphago_amd.models.policy_value import ResnetPolicyValue
     from rocalphago_amd.training.data import TRANSFORM_NAMES, DeviceDataset
     from rocalphago_amd.training.supervised import PolicyValueTrainer, SupervisedTrainer
-    kw = dict(board=19, filters_per_layer=filters, layers=layers, device=dev, seed=1)
+    col_kw = dict(board=19, filters_per_layer=filters, layers=layers, device=dev, seed=1)
+    kw = dict(col_kw, bn_axis=bn_axis)
     n = 4 * B
-    out = {"raw_top": bool(ResnetDualPlan.RAW_TOP)}
+    out = {"raw_top": bool(ResnetDualPlan.RAW_TOP), "bn_axis": bn_axis}
     index = [torch.randperm(n, device=dev)[:B] for _ in range(4)]
 
     def rate(step):
@@ -127,10 +183,36 @@ def sl_steps(B, filters, layers, steps, warmup, dev):
         finally:
             ResnetDualPlan.RAW_TOP = default
         assert type(tr.plan) is ResnetDualPlan and tr.plan.trunk.top_relu_in == raw
+        assert tr.plan.trunk.bn_axis == bn_axis
         out[key] = rate(tr.step)
         m = tr.pop_metrics()
         assert all(v == v for v in m), m
         del tr, dual
+
+    # the column network without its fused BN kernels (every BN the statistics / apply / conv
+    # sequence the channel trunk runs), and, next to a channel run, as it ships
+    for key, fused in (("resdual_step_column_unfused_positions_per_s", False),
+                       ("resdual_step_column_fused_positions_per_s", True)):
+        if fused and bn_axis != 1:
+            continue
+        mode = ResTrunk.WINO_MODE
+        ResTrunk.WINO_MODE = mode if fused else "0"
+        try:
+            dual = ResnetPolicyValue(VALUE_FEATURES, **col_kw).model
+            dual.compile(loss=["categorical_crossentropy", "mse"], optimizer=K.SGD(lr=0.003),
+                         metrics=["accuracy"])
+            tr = PolicyValueTrainer(dual, ds, B, TRANSFORM_NAMES, None, seed=1, targets="visits")
+        finally:
+            ResTrunk.WINO_MODE = mode
+        trunk = tr.plan.trunk
+        assert trunk.bn_axis == -1
+        if not fused:
+            assert not any(trunk._wino)
+            trunk.bn_prologue = False
+            trunk._wino_plans.clear()
+        out[key] = rate(tr.step)
+        assert fused or not any(trunk._fused)
+        del tr, dual, trunk
 
     pol = ResnetPolicy(DEFAULT_FEATURES, **kw).model
     pol.compile(loss="categorical_crossentropy", optimizer=K.SGD(lr=0.003), metrics=["accuracy"])
@@ -141,7 +223,7 @@ def sl_steps(B, filters, layers, steps, warmup, dev):
     return out
 
 
-def search(filters, layers, playouts, moves, dev):
+def search(filters, layers, playouts, moves, dev, bn_axis=-1):
     """mcts_bench.measure's loop (it builds its own networks, so the loop is repeated here) on
     a ParallelMCTS with the residual policy-value network."""
     from rocalphago_amd.engine.gamestate import GameState
@@ -149,7 +231,7 @@ def search(filters, layers, playouts, moves, dev):
     from rocalphago_amd.models.policy_value import ResnetPolicyValue
     from rocalphago_amd.search.apv import ParallelMCTS
     net = ResnetPolicyValue(DEFAULT_FEATURES + ["color"], board=19, filters_per_layer=filters,
-                            layers=layers, device=dev, seed=1)
+                            layers=layers, device=dev, seed=1, bn_axis=bn_axis)
     mc = ParallelMCTS(net, None, lmbda=0.5, batch=512, rollout_device="gpu", rollouts_per_leaf=1,
                       nthreads=16, seed=1, pipeline=3, max_inflight=8, rollout_group=8)
     mc.n_playout = playouts
@@ -180,15 +262,22 @@ def main():
     ap.add_argument("--moves", type=int, default=6)
     ap.add_argument("--skip-search", action="store_true")
     ap.add_argument("--skip-steps", action="store_true")
+    ap.add_argument("--skip-heads", action="store_true")
+    ap.add_argument("--bn-axis", type=int, choices=[-1, 1], default=-1,
+                    help="BatchNormalization axis of the networks: -1 column, 1 channel")
     args = ap.parse_args()
     dev = torch.device("cuda")
     res = {"metric": "residual policy-value network (19x19, B = %d, %d filters, %d layers)"
            % (args.batch, args.filters, args.layers), "batch": args.batch}
-    res["head_us"] = {str(B): head_kernels(B, args.filters, dev) for B in (256, 512)}
+    if not args.skip_heads:
+        res["head_us"] = {str(B): head_kernels(B, args.filters, dev) for B in (256, 512)}
+    res["bn_us"] = bn_kernels(args.filters, dev)
     if not args.skip_steps:
-        res.update(sl_steps(args.batch, args.filters, args.layers, args.steps, args.warmup, dev))
+        res.update(sl_steps(args.batch, args.filters, args.layers, args.steps, args.warmup, dev,
+                            args.bn_axis))
     if not args.skip_search:
-        res.update(search(args.filters, args.layers, args.playouts, args.moves, dev))
+        res.update(search(args.filters, args.layers, args.playouts, args.moves, dev,
+                          args.bn_axis))
     print(json.dumps(res))
 
 

@@ -15,6 +15,7 @@
 //   rag_bn_apply       out = act(c0[w]*x + c1[w]*dy + c2[w] + res) over the interior, zero padded
 //                      channels: forward BN+ReLU (c1 = 0), the final ReLU (no coefficients) and
 //                      the BN backward with the residual gradient added (act = identity)
+//   rag_bn_ch_*        the same four for one statistic per CHANNEL (axis=1), at the end of the file
 // All are HBM-bound streaming kernels (one or two reads + one write of a 29 MB activation at
 // B=256, K=128); the conv epilogue does the residual sum of the forward (conv.hip `res`).
 #include "common.h"
@@ -155,11 +156,13 @@ __global__ void __launch_bounds__(kT) bn_reduce_kernel(const bf16* __restrict__ 
   }
 }
 
-// One block per column w: 256 threads stride over the nblk partials (double accumulation),
-// wave shuffles + LDS combine them, thread 0 finishes the column.
+// One block per slot w (column, or channel of the channel form): 256 threads stride over the
+// nblk partials (double accumulation), wave shuffles + LDS combine them, thread 0 finishes the
+// slot. Slots >= nreal (padded channels) get zero statistics and coefficients and never index
+// gamma / beta / the running arrays.
 template <int MODE>
 __global__ void __launch_bounds__(kT) bn_finalize_kernel(const float* __restrict__ part, int nblk,
-                                                          int S, BNArgs a) {
+                                                          int S, int nreal, BNArgs a) {
   __shared__ double red[2][kT / 64];
   const int w = blockIdx.x;
   const int t = threadIdx.x, g = t >> 6, lane = t & 63;
@@ -176,6 +179,11 @@ __global__ void __launch_bounds__(kT) bn_finalize_kernel(const float* __restrict
   }
   __syncthreads();
   if (t) return;
+  if (w >= nreal) {
+    if (MODE == 0) a.stats[w] = a.stats[S + w] = 0.f;
+    a.coef[w] = a.coef[S + w] = a.coef[2 * S + w] = 0.f;
+    return;
+  }
   s0 = red[0][0] + red[0][1] + red[0][2] + red[0][3];
   s1 = red[1][0] + red[1][1] + red[1][2] + red[1][3];
   bn_finish_col<MODE>(a, S, w, s0, s1);
@@ -306,7 +314,7 @@ RAG_API int rag_bn_train_fwd(const void* X, int hx, int B, int S, int C, int CP,
                  nullptr, nullptr};
   bn_reduce_kernel<0><<<nblk, kT, 0, stream>>>((const bf16*)X, hx, nullptr, 0, nullptr,
                                                work, R, S, CP, rpb);
-  bn_finalize_kernel<0><<<S, kT, 0, stream>>>(work, nblk, S, a);
+  bn_finalize_kernel<0><<<S, kT, 0, stream>>>(work, nblk, S, S, a);
   return (int)hipGetLastError();
 }
 
@@ -328,7 +336,7 @@ RAG_API int rag_bn_bwd_coef(const void* X, int hx, const void* DY, int hd, int B
                  coef, dgamma, dbeta};
   bn_reduce_kernel<1><<<nblk, kT, 0, stream>>>((const bf16*)X, hx, (const bf16*)DY, hd, stats,
                                                work, R, S, CP, rpb);
-  bn_finalize_kernel<1><<<S, kT, 0, stream>>>(work, nblk, S, a);
+  bn_finalize_kernel<1><<<S, kT, 0, stream>>>(work, nblk, S, S, a);
   return (int)hipGetLastError();
 }
 
@@ -342,7 +350,7 @@ RAG_API int rag_bn_finalize_fwd(const float* part, int nblk, int B, int S, int C
   if (S > 64) return -1;
   const BNArgs a{(double)B * S * C, eps, momentum, gamma, beta, rmean, rvar, stats, coef,
                  nullptr, nullptr};
-  bn_finalize_kernel<0><<<S, kT, 0, stream>>>(part, nblk, S, a);
+  bn_finalize_kernel<0><<<S, kT, 0, stream>>>(part, nblk, S, S, a);
   return (int)hipGetLastError();
 }
 
@@ -352,7 +360,7 @@ RAG_API int rag_bn_finalize_bwd(const float* part, int nblk, int B, int S, int C
   if (S > 64) return -1;
   const BNArgs a{(double)B * S * C, 0.f, 0.f, gamma, nullptr, nullptr, nullptr, (float*)stats,
                  coef, dgamma, dbeta};
-  bn_finalize_kernel<1><<<S, kT, 0, stream>>>(part, nblk, S, a);
+  bn_finalize_kernel<1><<<S, kT, 0, stream>>>(part, nblk, S, S, a);
   return (int)hipGetLastError();
 }
 
@@ -386,5 +394,214 @@ RAG_API int rag_bn_apply_bwd_part(const float* part, int nblk, const float* gamm
   bn_apply_part_kernel<<<(int)nb, kT, 0, stream>>>(part, nblk, a, (const bf16*)X, hx,
                                                    (const bf16*)DY, hd, (const bf16*)RES, hr,
                                                    (bf16*)O, ho, B, S, C, CP);
+  return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// Channel BatchNorm (axis=1: one statistic per channel c, reduced over (b, h, w); the residual
+// tower of He et al. / AlphaGo Zero). Same layout, n = CP slots of which the first C are real:
+// padded slots get coefficients 0 and never index gamma / beta / the running arrays (C entries).
+//
+// Thread mapping of the reduction: a 16-byte vector holds 8 consecutive channels, so vector v of
+// a pixel covers channels 8v..8v+7 and CPV = CP/8 vectors make a pixel (16 at CP = 128, 24 at
+// 192, which does not divide 256). Only TA = (256 / CPV) * CPV threads are active (256 at 128
+// channels, 240 at 192): thread t owns vector t % CPV of pixels t / CPV, t / CPV + TA / CPV, ...
+// of its block's pixel range, so its 2 x 8 running sums always belong to the same 8 channels. The
+// block then adds the TA / CPV pixel lanes of each channel in LDS in a fixed order: no atomics,
+// bit-identical partials [nblk][2][CP] on every run; bn_finalize_kernel sums them in double.
+namespace {
+
+__device__ __forceinline__ size_t pix_offset(int pix, int S, int W, int halo, int CP) {
+  const int w = pix % S;
+  const int bh = pix / S;
+  const int h = bh % S;
+  const int b = bh / S;
+  return ((size_t)(b * W + h + halo) * W + w + halo) * CP;
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(kT) bn_ch_reduce_kernel(const bf16* __restrict__ X, int hx,
+                                                           const bf16* __restrict__ DY, int hd,
+                                                           const float* __restrict__ stats,
+                                                           float* __restrict__ part, int NPIX,
+                                                           int S, int CP, int pix_per_blk) {
+  __shared__ float red[2][kT * 8];
+  const int t = threadIdx.x;
+  const int CPV = CP / 8;
+  const int lanes = kT / CPV;  // pixel lanes; threads >= lanes * CPV idle
+  const int cv = t % CPV, lane = t / CPV;
+  const int WX = S + 2 * hx, WD = S + 2 * hd;
+  float a0[8], a1[8], mu[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    a0[e] = 0.f;
+    a1[e] = 0.f;
+    mu[e] = (MODE == 1 && lane < lanes) ? stats[cv * 8 + e] : 0.f;
+  }
+  const int p0 = blockIdx.x * pix_per_blk;
+  const int p1 = min(NPIX, p0 + pix_per_blk);
+  if (lane < lanes) {
+    for (int pix = p0 + lane; pix < p1; pix += lanes) {
+      float x[8];
+      load8(X + pix_offset(pix, S, WX, hx, CP) + cv * 8, x);
+      if (MODE == 0) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          a0[e] += x[e];
+          a1[e] = fmaf(x[e], x[e], a1[e]);
+        }
+      } else {
+        float d[8];
+        load8(DY + pix_offset(pix, S, WD, hd, CP) + cv * 8, d);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          a0[e] += d[e];
+          a1[e] = fmaf(d[e], x[e] - mu[e], a1[e]);
+        }
+      }
+    }
+    // red[q][lane][c]: the final sums read consecutive c from consecutive threads
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      red[0][lane * CP + cv * 8 + e] = a0[e];
+      red[1][lane * CP + cv * 8 + e] = a1[e];
+    }
+  }
+  __syncthreads();
+  for (int o = t; o < 2 * CP; o += kT) {
+    const int q = o / CP, c = o - q * CP;
+    float s = 0.f;
+    for (int l = 0; l < lanes; ++l) s += red[q][l * CP + c];
+    part[((size_t)blockIdx.x * 2 + q) * CP + c] = s;
+  }
+}
+
+// Inference coefficients from the running statistics: one thread per channel slot.
+__global__ void __launch_bounds__(kT) bn_ch_infer_kernel(BNArgs a, int C, int CP) {
+  const int c = blockIdx.x * kT + threadIdx.x;
+  if (c >= CP) return;
+  if (c < C) {
+    bn_finish_col<2>(a, CP, c, 0.0, 0.0);
+  } else {
+    a.coef[c] = 0.f;
+    a.coef[CP + c] = 0.f;
+    a.coef[2 * CP + c] = 0.f;
+  }
+}
+
+__device__ __forceinline__ void loadf8(const float* p, float (&v)[8]) {
+  const float4 lo = *reinterpret_cast<const float4*>(p);
+  const float4 hi = *reinterpret_cast<const float4*>(p + 4);
+  v[0] = lo.x, v[1] = lo.y, v[2] = lo.z, v[3] = lo.w;
+  v[4] = hi.x, v[5] = hi.y, v[6] = hi.z, v[7] = hi.w;
+}
+
+// out = act(c0[c]*x + c1[c]*dy + c2[c] + res) over the interior, grid-stride; the 8 coefficients
+// of a vector are contiguous (two 16-byte loads per coefficient row, L2-resident).
+__global__ void __launch_bounds__(kT) bn_ch_apply_kernel(
+    const bf16* __restrict__ X, int hx, const bf16* __restrict__ DY, int hd,
+    const bf16* RES, int hr, bf16* O, int ho,  // RES may alias O (in-place skip gradient)
+    const float* __restrict__ coef, int relu, int B, int S, int C, int CP) {
+  const int CPV = CP / 8;
+  const int total = B * S * S * CPV;  // < 2^31 (checked by the launcher)
+  const int WX = S + 2 * hx, WD = S + 2 * hd, WR = S + 2 * hr, WO = S + 2 * ho;
+  for (int i = blockIdx.x * kT + threadIdx.x; i < total; i += gridDim.x * kT) {
+    const int cv = i % CPV;
+    const int pix = i / CPV;
+    const int c0 = cv * 8;
+    bf16x8 o;
+    if (c0 >= C) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] = (bf16)0.f;
+    } else {
+      float x[8], cx[8], cc[8], v[8];
+      load8(X + pix_offset(pix, S, WX, hx, CP) + c0, x);
+      loadf8(coef + c0, cx);
+      loadf8(coef + 2 * CP + c0, cc);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = fmaf(cx[e], x[e], cc[e]);
+      if (DY) {
+        float d[8], cd[8];
+        load8(DY + pix_offset(pix, S, WD, hd, CP) + c0, d);
+        loadf8(coef + CP + c0, cd);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = fmaf(cd[e], d[e], v[e]);
+      }
+      if (RES) {
+        float r[8];
+        load8(RES + pix_offset(pix, S, WR, hr, CP) + c0, r);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] += r[e];
+      }
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float y = relu ? fmaxf(v[e], 0.f) : v[e];
+        o[e] = (bf16)((c0 + e) < C ? y : 0.f);
+      }
+    }
+    *reinterpret_cast<bf16x8*>(O + pix_offset(pix, S, WO, ho, CP) + c0) = o;
+  }
+}
+
+// CP/8 vectors of a pixel must fit one block's threads, and B*S*S pixels an int.
+bool ch_shape_ok(int B, int S, int C, int CP) {
+  return B > 0 && S > 0 && C > 0 && C <= CP && CP % 8 == 0 && CP / 8 <= kT &&
+         (size_t)B * S * S * (CP / 8) < (1u << 31);
+}
+
+}  // namespace
+
+// Floats of workspace rag_bn_ch_train_fwd / rag_bn_ch_bwd_coef need (per-block partials).
+RAG_API int rag_bn_ch_workspace(int B, int S, int CP) {
+  return reduce_blocks(B * S * S) * 2 * CP;
+}
+
+RAG_API int rag_bn_ch_train_fwd(const void* X, int hx, int B, int S, int C, int CP,
+                                const float* gamma, const float* beta, float* rmean, float* rvar,
+                                float eps, float momentum, float* stats, float* coef, float* work,
+                                hipStream_t stream) {
+  if (!ch_shape_ok(B, S, C, CP)) return -1;
+  const int NPIX = B * S * S, nblk = reduce_blocks(NPIX);
+  const int ppb = (NPIX + nblk - 1) / nblk;
+  const BNArgs a{(double)B * S * S, eps, momentum, gamma, beta, rmean, rvar, stats, coef,
+                 nullptr, nullptr};
+  bn_ch_reduce_kernel<0><<<nblk, kT, 0, stream>>>((const bf16*)X, hx, nullptr, 0, nullptr, work,
+                                                  NPIX, S, CP, ppb);
+  bn_finalize_kernel<0><<<CP, kT, 0, stream>>>(work, nblk, CP, C, a);
+  return (int)hipGetLastError();
+}
+
+RAG_API int rag_bn_ch_infer_coef(const float* gamma, const float* beta, float* rmean, float* rvar,
+                                 float eps, int C, int CP, float* coef, hipStream_t stream) {
+  if (C <= 0 || C > CP || CP % 8) return -1;
+  const BNArgs a{1.0, eps, 0.f, gamma, beta, rmean, rvar, nullptr, coef, nullptr, nullptr};
+  bn_ch_infer_kernel<<<(CP + kT - 1) / kT, kT, 0, stream>>>(a, C, CP);
+  return (int)hipGetLastError();
+}
+
+RAG_API int rag_bn_ch_bwd_coef(const void* X, int hx, const void* DY, int hd, int B, int S, int C,
+                               int CP, const float* gamma, const float* stats, float* dgamma,
+                               float* dbeta, float* coef, float* work, hipStream_t stream) {
+  if (!ch_shape_ok(B, S, C, CP)) return -1;
+  const int NPIX = B * S * S, nblk = reduce_blocks(NPIX);
+  const int ppb = (NPIX + nblk - 1) / nblk;
+  const BNArgs a{(double)B * S * S, 0.f, 0.f, gamma, nullptr, nullptr, nullptr, (float*)stats,
+                 coef, dgamma, dbeta};
+  bn_ch_reduce_kernel<1><<<nblk, kT, 0, stream>>>((const bf16*)X, hx, (const bf16*)DY, hd, stats,
+                                                  work, NPIX, S, CP, ppb);
+  bn_finalize_kernel<1><<<CP, kT, 0, stream>>>(work, nblk, CP, C, a);
+  return (int)hipGetLastError();
+}
+
+RAG_API int rag_bn_ch_apply(const void* X, int hx, const void* DY, int hd, const void* RES, int hr,
+                            void* O, int ho, const float* coef, int relu, int B, int S, int C,
+                            int CP, hipStream_t stream) {
+  if (!ch_shape_ok(B, S, C, CP) || !coef || ((uintptr_t)coef & 15)) return -1;
+  const size_t total = (size_t)B * S * S * (CP / 8);
+  size_t nb = (total + kT - 1) / kT;
+  if (nb > 8192) nb = 8192;
+  bn_ch_apply_kernel<<<(int)nb, kT, 0, stream>>>((const bf16*)X, hx, (const bf16*)DY, hd,
+                                                 (const bf16*)RES, hr, (bf16*)O, ho, coef, relu,
+                                                 B, S, C, CP);
   return (int)hipGetLastError();
 }

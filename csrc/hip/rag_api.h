@@ -165,6 +165,20 @@ RAG_API int rag_bn_apply_bwd_part(const float* part, int nblk, const float* gamm
                                   const float* stats, float* dgamma, float* dbeta, const void* X,
                                   int hx, const void* DY, int hd, const void* RES, int hr, void* O,
                                   int ho, int B, int S, int C, int CP, hipStream_t stream);
+// channel form (axis=1): one statistic per channel, CP slots of which the first C are real
+RAG_API int rag_bn_ch_workspace(int B, int S, int CP);
+RAG_API int rag_bn_ch_train_fwd(const void* X, int hx, int B, int S, int C, int CP,
+                                const float* gamma, const float* beta, float* rmean, float* rvar,
+                                float eps, float momentum, float* stats, float* coef, float* work,
+                                hipStream_t stream);
+RAG_API int rag_bn_ch_infer_coef(const float* gamma, const float* beta, float* rmean, float* rvar,
+                                 float eps, int C, int CP, float* coef, hipStream_t stream);
+RAG_API int rag_bn_ch_bwd_coef(const void* X, int hx, const void* DY, int hd, int B, int S, int C,
+                               int CP, const float* gamma, const float* stats, float* dgamma,
+                               float* dbeta, float* coef, float* work, hipStream_t stream);
+RAG_API int rag_bn_ch_apply(const void* X, int hx, const void* DY, int hd, const void* RES, int hr,
+                            void* O, int ho, const float* coef, int relu, int B, int S, int C,
+                            int CP, hipStream_t stream);
 
 // ---- features.hip, ladder.hip, rollout.hip
 RAG_API int rag_features(const void* colors, const void* ages, const int32_t* meta,

@@ -441,7 +441,8 @@ class HipTrunk(_PackedConvs):
 
 
 class BNSpec(object):
-    """One column BatchNormalization (Keras-1 axis=-1 on (B, C, H, W) tensors: S statistics)."""
+    """One BatchNormalization on (B, C, H, W) tensors: column (Keras-1 axis=-1, S statistics) or
+    channel (axis=1, K statistics); ResTrunk's ``bn_axis`` says which and checks the lengths."""
     __slots__ = ("eps", "momentum", "gamma", "beta", "rmean", "rvar", "dgamma", "dbeta")
 
     def __init__(self, eps, momentum, params, grads):
@@ -474,16 +475,27 @@ class ResTrunk(_PackedConvs):
     conv l use halo hin[l] = max(1, ks_l // 2), so wgrad always runs the all-taps kernel and the
     dgrad input is wide enough (the reference's filter_width_1 also sets the FIRST unit's conv,
     5x5 by default). Memory: (units + BNs + ~4) activations of B x (S+2)^2 x K bf16 (29 MB each
-    at B=256, K=128) — trivial against 288 GB of HBM."""
+    at B=256, K=128) — trivial against 288 GB of HBM.
+
+    ``bn_axis=1`` (one statistic per channel, the residual tower of He et al. / AlphaGo Zero;
+    the default -1 is the reference's column BN above): every BN runs the unfused sequence on
+    the channel kernels (bn.hip rag_bn_ch_*) -- statistics or running coefficients, one BN+ReLU
+    pass into U, the plain conv with the residual epilogue; backward wgrad, dgrad masked by U,
+    the channel backward reduction and one apply that adds the skip gradient. No BN prologue,
+    no Winograd BN kernel, and stats / coef hold one slot per padded channel."""
 
     # 3x3 128 -> 128 layers whose input BN is fused run the Winograd BN kernel: "0" off, "1"
     # forward only (default), "2" forward and dgrad (see __init__)
     WINO_MODE = "1"
     DEFER_REDUCE = True
 
-    def __init__(self, specs, units, bns, board, device, raw_top=False):
+    def __init__(self, specs, units, bns, board, device, raw_top=False, bn_axis=-1):
         assert specs and len(specs) == 1 + sum(units) == 1 + len(bns)
+        if bn_axis not in (-1, 1):
+            raise ValueError("ResTrunk: bn_axis must be -1 (column) or 1 (channel), got %r"
+                             % (bn_axis,))
         self.specs, self.units, self.bns = specs, list(units), bns
+        self.bn_axis = bn_axis
         self.S = board
         self.device = device
         # the head reads A_U and applies the ReLU itself: no H = ReLU(A_U) pass
@@ -493,6 +505,14 @@ class ResTrunk(_PackedConvs):
         for s in specs[1:]:
             assert s.cin == K and s.cout == K, "residual trunk needs constant width"
         self.K, self.KP = K, specs[0].coutp
+        # a checkpoint of the other kind must fail here, not read out of bounds in a kernel
+        slots = K if bn_axis == 1 else board
+        for j, bn in enumerate(bns):
+            for name in ("gamma", "beta", "rmean", "rvar", "dgamma", "dbeta"):
+                t = getattr(bn, name)
+                if t is not None and t.numel() != slots:
+                    raise ValueError("ResTrunk: BN %d %s has %d entries, bn_axis=%d needs %d"
+                                     % (j, name, t.numel(), bn_axis, slots))
         self._B = 0
         # 3x3 128 -> 128 layers whose input BN is fused (_prologue_ok) run the Winograd kernel
         # with the BN built into its input transform (conv_wino.hip WinoBN) at batches that fill
@@ -501,7 +521,8 @@ class ResTrunk(_PackedConvs):
         # (51.6 vs 48.6 us on the direct kernel; standalone it is 37.4 us + a 16.6 us reduction,
         # and riding in the BN backward apply made that pass 47.9 instead of 18.5 us). ResNet
         # 71.6 k (1) / 70.9 k (2) / 69.7 k (2, no deferral) / 68.0 k (0) positions/s on one box.
-        mode = str(self.WINO_MODE) if device.type == "cuda" else "0"
+        # (channel BN has no fused kernel: no Winograd layers, no packing tables for them)
+        mode = str(self.WINO_MODE) if device.type == "cuda" and bn_axis != 1 else "0"
         wino = [mode != "0" and l > 0 and s.ks == 3 and s.cinp == s.coutp == 128
                 and ops.conv_wino_ok(board, 1, s.cinp, s.coutp, 3) for l, s in enumerate(specs)]
         self._init_packing(specs, device, wino)
@@ -549,15 +570,21 @@ class ResTrunk(_PackedConvs):
         self.G = {h: alloc(B, S, h, KP, dev) for h in set(self.hin) | {1}}
         self.gI = {h: alloc(B, S, h, KP, dev) for h in inner_h}
         self.dU = alloc(B, S, 1, KP, dev)
-        self.stats = torch.zeros((nb, 2, S), dtype=torch.float32, device=dev)
-        self.coef = torch.zeros((nb, 3, S), dtype=torch.float32, device=dev)
-        self.bcoef = torch.zeros((3, S), dtype=torch.float32, device=dev)
-        # BN column-statistics partials written by the fused conv epilogues (forward: one per
-        # BN, whose input that conv produced; backward: one, reused layer by layer)
-        # (the Winograd kernel writes one partial per board)
-        nblk = max(ops.conv_bn_stat_blocks(B, S, KP), B) if KP % 128 == 0 and KP % 192 else 1
-        self.spart = torch.zeros((nb, nblk, 2, S), dtype=torch.float32, device=dev)
-        self.bpart = torch.zeros((nblk, 2, S), dtype=torch.float32, device=dev)
+        # one slot per column, or per padded channel (bn_axis=1; padded slots hold 0)
+        n = KP if self.bn_axis == 1 else S
+        self.stats = torch.zeros((nb, 2, n), dtype=torch.float32, device=dev)
+        self.coef = torch.zeros((nb, 3, n), dtype=torch.float32, device=dev)
+        self.bcoef = torch.zeros((3, n), dtype=torch.float32, device=dev)
+        if self.bn_axis == 1:  # nothing fused: no conv epilogue writes statistics
+            self.spart = self.bpart = None
+        else:
+            # BN column-statistics partials written by the fused conv epilogues (forward: one
+            # per BN, whose input that conv produced; backward: one, reused layer by layer)
+            # (the Winograd kernel writes one partial per board)
+            nblk = max(ops.conv_bn_stat_blocks(B, S, KP), B) if KP % 128 == 0 and KP % 192 \
+                else 1
+            self.spart = torch.zeros((nb, nblk, 2, S), dtype=torch.float32, device=dev)
+            self.bpart = torch.zeros((nblk, 2, S), dtype=torch.float32, device=dev)
         need = max(ops._lib().rag_conv_wgrad_workspace(B, S, s.coutp, s.cinp, s.ks, None)
                    for s in self.specs)
         self._work = torch.empty(need + 1024, dtype=torch.float32, device=dev)
@@ -585,6 +612,8 @@ class ResTrunk(_PackedConvs):
         128-channel ping-pong / slab kernels (3x3, unpadded width, a grid that fills the chip);
         other layers keep the bn_apply pass. bn_prologue = False disables it."""
         sp = self.specs[j + 1]
+        if self.bn_axis == 1:  # the prologue kernels apply per-column coefficients
+            return False
         return (self.bn_prologue and sp.ks == 3 and self.hin[j + 1] == 1 and self.K == self.KP
                 and ops.conv_bn_fusable(B, self.S, 1, sp.cinp, sp.coutp, sp.ks))
 
@@ -616,6 +645,7 @@ class ResTrunk(_PackedConvs):
         j = 0
         nb = len(self.bns)
         fused, wino = self._plan(B)
+        ch = self.bn_axis == 1
         self._fused = list(fused)
         stat_ready = [False] * nb  # BN j's input statistics came out of the conv producing it
         for u, n in enumerate(self.units):
@@ -627,8 +657,12 @@ class ResTrunk(_PackedConvs):
                                         bn.rmean, bn.rvar, bn.eps, bn.momentum, self.stats[j],
                                         self.coef[j])
                 elif training:
-                    ops.bn_train_fwd(x, B, S, K, bn.gamma, bn.beta, bn.rmean, bn.rvar, bn.eps,
-                                     bn.momentum, self.stats[j], self.coef[j])
+                    (ops.bn_ch_train_fwd if ch else ops.bn_train_fwd)(
+                        x, B, S, K, bn.gamma, bn.beta, bn.rmean, bn.rvar, bn.eps, bn.momentum,
+                        self.stats[j], self.coef[j])
+                elif ch:
+                    ops.bn_ch_infer_coef(bn.gamma, bn.beta, bn.rmean, bn.rvar, bn.eps, K,
+                                         self.KP, self.coef[j])
                 else:
                     ops.bn_infer_coef(bn.gamma, bn.beta, bn.rmean, bn.rvar, bn.eps, S,
                                       self.coef[j])
@@ -650,7 +684,8 @@ class ResTrunk(_PackedConvs):
                     if sp_out is not None:
                         stat_ready[l] = True
                 else:
-                    ops.bn_apply(x, U, B, S, K, coef=self.coef[j], relu=True)
+                    (ops.bn_ch_apply if ch else ops.bn_apply)(x, U, B, S, K, coef=self.coef[j],
+                                                              relu=True)
                     ops.conv_igemm(U, self._wf[l], self._bias[l], y, B, S, self.hin[l], 1,
                                    sp.cinp, sp.coutp, sp.ks, False, residual=res)
                 j += 1
@@ -666,6 +701,7 @@ class ResTrunk(_PackedConvs):
         by then)."""
         S, K = self.S, self.K
         wino = self._plan(B)[1]
+        ch = self.bn_axis == 1
         cur, hcur = self.G[1][:B], 1  # dL/dA_{u+1}
         for u in range(len(self.units) - 1, -1, -1):
             n, jend = self.units[u], self._unit_last[u]
@@ -725,10 +761,11 @@ class ResTrunk(_PackedConvs):
                                             B, S, K, bn.gamma, self.stats[j], bn.dgamma,
                                             bn.dbeta, self.bcoef)
                     else:
-                        ops.bn_bwd_coef(x, dU, B, S, K, bn.gamma, self.stats[j], bn.dgamma,
-                                        bn.dbeta, self.bcoef)
-                    ops.bn_apply(x, out, B, S, K, coef=self.bcoef, relu=False, dy=dU,
-                                 residual=res)
+                        (ops.bn_ch_bwd_coef if ch else ops.bn_bwd_coef)(
+                            x, dU, B, S, K, bn.gamma, self.stats[j], bn.dgamma, bn.dbeta,
+                            self.bcoef)
+                    (ops.bn_ch_apply if ch else ops.bn_apply)(
+                        x, out, B, S, K, coef=self.bcoef, relu=False, dy=dU, residual=res)
                 if on_layer_done is not None:  # dW[l] final (its reduction ran by now)
                     on_layer_done(l)
                 if i > 0:

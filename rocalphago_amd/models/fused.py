@@ -70,9 +70,10 @@ def detect_plan(model):
 
 class _TrunkPlan(object):
     def __init__(self, model, convs, head_conv, res=None):
-        """res: None for a straight run of convolutions (HipTrunk), or (bns, units, raw_top) for
-        the residual trunk (ResTrunk: BatchNormalization layers, convs per unit, and whether
-        the head reads the last residual sum itself)."""
+        """res: None for a straight run of convolutions (HipTrunk), or (bns, units, raw_top[,
+        bn_axis]) for the residual trunk (ResTrunk: BatchNormalization layers, convs per unit,
+        whether the head reads the last residual sum itself, and the BN axis: -1 column
+        (default), 1 channel)."""
         net = model.net
         self.model = model
         self.net = net
@@ -85,10 +86,12 @@ class _TrunkPlan(object):
         if res is None:
             self.trunk = HipTrunk(specs, self.S, net.device)
         else:
-            bns, units, raw_top = res
+            bns, units, raw_top = res[:3]
+            bn_axis = res[3] if len(res) > 3 else -1
             bspecs = [BNSpec(ld.config.get("epsilon", 1e-3), ld.config.get("momentum", 0.99),
                              net.params_of(ld.name), net.grads_of(ld.name)) for ld in bns]
-            self.trunk = ResTrunk(specs, units, bspecs, self.S, net.device, raw_top=raw_top)
+            self.trunk = ResTrunk(specs, units, bspecs, self.S, net.device, raw_top=raw_top,
+                                  bn_axis=bn_axis)
         self.conv_names = [ld.name for ld in convs]
         self.head_name = head_conv.name
         self.K = specs[-1].cout
@@ -476,7 +479,8 @@ def _act(ld, src, name):
 def _match_res_trunk(model):
     """The residual trunk both ResNet plans share, up to and including its final ReLU (a
     topologically ordered layer list): (convs, bns, units, the ReLU's name, the layers behind
-    it), or None."""
+    it, the BN axis: -1 column / 1 channel), or None. Every BatchNormalization must use the same
+    axis: a mixed model runs the generic executor."""
     L = model.layers
     S = model.input_shape[-1] if model.input_shape else None
     if not S or S > 25 or len(L) < 8 or L[0].class_name != "InputLayer":
@@ -486,7 +490,7 @@ def _match_res_trunk(model):
     def bn_ok(ld, src):
         c = ld.config
         return (ld.class_name == "BatchNormalization" and ld.inbound == [src] and
-                c.get("mode", 0) == 0 and c.get("axis", -1) in (-1, 3))
+                c.get("mode", 0) == 0 and c.get("axis", -1) in (-1, 3, 1, -3))
 
     if not conv(L[1], L[0].name):
         return None
@@ -512,7 +516,10 @@ def _match_res_trunk(model):
     K = L[1].config["nb_filter"]
     if any(c.config["nb_filter"] != K for c in convs):
         return None
-    return convs, bns, units, L[i].name, L[i + 1:]
+    axes = set(1 if ld.config.get("axis", -1) in (1, -3) else -1 for ld in bns)
+    if len(axes) != 1:
+        return None
+    return convs, bns, units, L[i].name, L[i + 1:], axes.pop()
 
 
 def _detect_resnet(model):
@@ -520,7 +527,7 @@ def _detect_resnet(model):
     m = _match_res_trunk(model)
     if m is None:
         return None
-    convs, bns, units, top, rest = m
+    convs, bns, units, top, rest, bn_axis = m
     pl = rest[3] if len(rest) == 5 and rest[3].class_name == "PassLogit" and \
         rest[3].inbound == [rest[2].name] else None
     if len(rest) != (5 if pl is not None else 4) or \
@@ -528,7 +535,7 @@ def _detect_resnet(model):
             rest[1].class_name != "Flatten" or rest[2].class_name != "Bias" or \
             not _act(rest[-1], rest[-2].name, "softmax"):
         return None
-    return ResnetPlan(model, convs, bns, units, rest[0], rest[2], pl)
+    return ResnetPlan(model, convs, bns, units, rest[0], rest[2], pl, bn_axis=bn_axis)
 
 
 def _detect_resnet_dual(model):
@@ -537,19 +544,20 @@ def _detect_resnet_dual(model):
     m = _match_res_trunk(model)
     if m is None or model.input_shape[-2] != model.input_shape[-1]:
         return None
-    convs, bns, units, top, rest = m
+    convs, bns, units, top, rest, bn_axis = m
     heads = _match_two_heads(model, rest, top)
-    return ResnetDualPlan(model, convs, bns, units, *heads) if heads else None
+    return ResnetDualPlan(model, convs, bns, units, *heads, bn_axis=bn_axis) if heads else None
 
 
 class ResnetPlan(PolicyPlan):
-    """ResnetPolicy on the HIP engine: ResTrunk (column BN + ReLU kernels, residual conv
-    epilogue) + the same fused policy head / loss as PolicyPlan. Training steps use batch
+    """ResnetPolicy on the HIP engine: ResTrunk (column or channel BN + ReLU kernels, residual
+    conv epilogue) + the same fused policy head / loss as PolicyPlan. Training steps use batch
     statistics (and update the running averages); forward / evaluation use the running ones,
     like Keras' learning phase."""
 
-    def __init__(self, model, convs, bns, units, head_conv, bias_layer, pass_layer=None):
-        _TrunkPlan.__init__(self, model, convs, head_conv, res=(bns, units, False))
+    def __init__(self, model, convs, bns, units, head_conv, bias_layer, pass_layer=None,
+                 bn_axis=-1):
+        _TrunkPlan.__init__(self, model, convs, head_conv, res=(bns, units, False, bn_axis))
         self.bias_name = bias_layer.name
         self.pass_name = pass_layer.name if pass_layer is not None else None
         self.head = PolicyHeadEngine(self.trunk, self.K, pass_logit=pass_layer is not None)
@@ -570,6 +578,7 @@ class ResnetDualPlan(DualPlan):
     RAW_TOP = True
 
     def __init__(self, model, convs, bns, units, head_conv, bias_layer, vhead_conv, dense1,
-                 dense2):
+                 dense2, bn_axis=-1):
         super(ResnetDualPlan, self).__init__(model, convs, head_conv, bias_layer, vhead_conv,
-                                             dense1, dense2, res=(bns, units, self.RAW_TOP))
+                                             dense1, dense2,
+                                             res=(bns, units, self.RAW_TOP, bn_axis))

@@ -79,8 +79,10 @@ class ResnetPolicy(CNNPolicy):
     """Residual policy (He et al. 2015) exactly as reference policy.py:141-271: linear input conv,
     units of n_skip_K x (BatchNorm -> ReLU -> conv) with sum-merge, final ReLU, 1x1 conv, Flatten,
     Bias, softmax. Note the reference's BatchNormalization uses Keras' default axis=-1 on 'th'
-    tensors; that axis is kept for checkpoint compatibility. ``pass_logit=True`` adds the learned
-    pass logit of CNNPolicy (softmax over S*S + 1, pass last)."""
+    tensors; that axis is kept for checkpoint compatibility and is the default. ``bn_axis=1``
+    builds every BatchNormalization with one statistic per channel instead (the residual tower of
+    He et al. / AlphaGo Zero; the JSON carries ``"axis": 1``). ``pass_logit=True`` adds the
+    learned pass logit of CNNPolicy (softmax over S*S + 1, pass last)."""
 
     @staticmethod
     def create_network(**kwargs):
@@ -110,6 +112,12 @@ class ResnetPolicy(CNNPolicy):
         network (models/policy_value.py ResnetPolicyValue) puts its two heads on the same
         trunk."""
         layers = []
+        # bn_axis: -1 (default) the reference's column statistics, 1 one statistic per channel
+        bn_axis = params.get("bn_axis", -1)
+        if bn_axis not in (-1, 1) or isinstance(bn_axis, bool):
+            raise ValueError("bn_axis must be -1 (column, the reference) or 1 (channel), got %r"
+                             % (bn_axis,))
+        bn_kw = {"axis": 1} if bn_axis == 1 else {}
 
         def add(layer, inbound):
             layer.inbound = list(inbound)
@@ -131,7 +139,7 @@ class ResnetPolicy(CNNPolicy):
             n_skip = params.get("n_skip_%d" % Kidx, 1)
             for i in range(n_skip):
                 layer = Kidx + i
-                path = add(K.BatchNormalization(), [path])
+                path = add(K.BatchNormalization(**bn_kw), [path])
                 path = add(K.Activation('relu'), [path])
                 fw = params.get("filter_width_%d" % layer, 3)
                 path = add(K.Convolution2D(nb_filter=params["filters_per_layer"], nb_row=fw,

@@ -130,7 +130,8 @@ class ResnetPolicyValue(CNNPolicyValue):
     @staticmethod
     def create_network(**kwargs):
         """ResnetPolicy's keyword args: input_dim, board (19), filters_per_layer (128), layers
-        (20), filter_width_1 (5), n_skip_K, filter_width_K; the value head's: dense (256),
+        (20), filter_width_1 (5), n_skip_K, filter_width_K, bn_axis (-1 column, 1 channel);
+        the value head's: dense (256),
         dense_activation ("relu"); device, seed. No pass logit."""
         params = {"board": 19, "filters_per_layer": 128, "layers": 20, "filter_width_1": 5,
                   "dense": 256, "dense_activation": "relu"}

@@ -67,6 +67,11 @@ SIGNATURES = {
     "rag_bn_apply_bwd_part": [P, I, P, P, P, P, P, I, P, I, P, I, P, I, I, I, I, I, P],
     "rag_bn_finalize_fwd": [P, I, I, I, I, P, P, P, P, F, F, P, P, P],
     "rag_bn_finalize_bwd": [P, I, I, I, I, P, P, P, P, P, P],
+    "rag_bn_ch_workspace": [I, I, I],
+    "rag_bn_ch_train_fwd": [P, I, I, I, I, I, P, P, P, P, F, F, P, P, P, P],
+    "rag_bn_ch_infer_coef": [P, P, P, P, F, I, I, P, P],
+    "rag_bn_ch_bwd_coef": [P, I, P, I, I, I, I, I, P, P, P, P, P, P, P],
+    "rag_bn_ch_apply": [P, I, P, I, P, I, P, I, P, I, I, I, I, I, P],
     # sample.hip
     "rag_sample_moves": [P, P, I, P, I, I, F, C.c_uint64, P, P, P],
     # features.hip

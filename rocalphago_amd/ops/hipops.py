@@ -414,6 +414,73 @@ def bn_apply_bwd_part(part, nblk, x, out, B, S, C, gamma, stats, dgamma, dbeta, 
     return out
 
 
+# ---- channel BatchNorm (bn.hip rag_bn_ch_*; axis=1). Per-channel vectors: gamma, beta, running
+# mean / var have C entries; stats [2, CP] and coef [3, CP] have one slot per PADDED channel (the
+# padded slots hold 0), so coef rows stay 16-byte aligned for the apply's vector loads.
+
+def bn_ch_workspace(B, S, CP, device):
+    n = _lib().rag_bn_ch_workspace(B, S, CP)
+    key = ("bn_ch", device)
+    buf = _ws_cache.get(key)
+    if buf is None or buf.numel() < n:
+        buf = torch.empty(n + 256, dtype=torch.float32, device=device)
+        _ws_cache[key] = buf
+    return buf
+
+
+def _ch_slots(t, rows, CP, what):
+    if t.numel() < rows * CP:
+        raise ValueError("%s needs %d x %d (padded channel) slots" % (what, rows, CP))
+
+
+def bn_ch_train_fwd(x, B, S, C, gamma, beta, rmean, rvar, eps, momentum, stats, coef):
+    """Batch statistics of x [pad] per channel (over b, h, w) -> stats (mean, rstd) [2, CP], coef
+    (affine) [3, CP], running averages [C] updated in place (skipped when rmean is None)."""
+    CP = x.shape[-1]
+    _ch_slots(stats, 2, CP, "bn_ch_train_fwd stats")
+    _ch_slots(coef, 3, CP, "bn_ch_train_fwd coef")
+    _check(_lib().rag_bn_ch_train_fwd(_ptr(x), _halo(x, S), B, S, C, CP, _ptr(gamma),
+                                      _ptr(beta), _ptr(rmean), _ptr(rvar), float(eps),
+                                      float(momentum), _ptr(stats), _ptr(coef),
+                                      _ptr(bn_ch_workspace(B, S, CP, x.device)), _stream()),
+           "bn_ch_train_fwd")
+
+
+def bn_ch_infer_coef(gamma, beta, rmean, rvar, eps, C, CP, coef):
+    _ch_slots(coef, 3, CP, "bn_ch_infer_coef coef")
+    _check(_lib().rag_bn_ch_infer_coef(_ptr(gamma), _ptr(beta), _ptr(rmean), _ptr(rvar),
+                                       float(eps), C, CP, _ptr(coef), _stream()),
+           "bn_ch_infer_coef")
+
+
+def bn_ch_bwd_coef(x, dy, B, S, C, gamma, stats, dgamma, dbeta, coef):
+    CP = x.shape[-1]
+    if dy.shape[-1] != CP:
+        raise ValueError("bn_ch_bwd_coef channel mismatch")
+    _ch_slots(stats, 2, CP, "bn_ch_bwd_coef stats")
+    _ch_slots(coef, 3, CP, "bn_ch_bwd_coef coef")
+    _check(_lib().rag_bn_ch_bwd_coef(_ptr(x), _halo(x, S), _ptr(dy), _halo(dy, S), B, S, C, CP,
+                                     _ptr(gamma), _ptr(stats), _ptr(dgamma), _ptr(dbeta),
+                                     _ptr(coef), _ptr(bn_ch_workspace(B, S, CP, x.device)),
+                                     _stream()), "bn_ch_bwd_coef")
+
+
+def bn_ch_apply(x, out, B, S, C, coef, relu=True, dy=None, residual=None):
+    """out = act(coef[0, c]*x + coef[1, c]*dy + coef[2, c] + residual) (interior; padded
+    channels 0). ``residual`` may be ``out`` itself."""
+    CP = x.shape[-1]
+    for t in (out, dy, residual):
+        if t is not None and t.shape[-1] != CP:
+            raise ValueError("bn_ch_apply channel mismatch")
+    _ch_slots(coef, 3, CP, "bn_ch_apply coef")
+    _check(_lib().rag_bn_ch_apply(_ptr(x), _halo(x, S), _ptr(dy),
+                                  0 if dy is None else _halo(dy, S), _ptr(residual),
+                                  0 if residual is None else _halo(residual, S), _ptr(out),
+                                  _halo(out, S), _ptr(coef), int(relu), B, S, C, CP, _stream()),
+           "bn_ch_apply")
+    return out
+
+
 _ws_cache = {}
 
 
