@@ -16,7 +16,8 @@ One JSON line:
     the two rows bracket its cost). The candidates alternate in the same process
     (dual_bench.alternate); ``spread`` is the largest max - min over a candidate's rounds;
   * --bn-axis 1 builds the networks with channel BatchNormalization (one statistic per
-    channel; ResTrunk's unfused channel kernels). resdual_step_column_unfused_positions_per_s is
+    channel; ResTrunk's channel kernels, unfused but for the Winograd forward of 128-wide
+    trunks). resdual_step_column_unfused_positions_per_s is
     always the column network's step with ``bn_prologue = False`` and ``WINO_MODE = "0"``, the
     launch-for-launch counterpart of the channel step, and with --bn-axis 1
     resdual_step_column_fused_positions_per_s the column step as it ships (the distance a fused
@@ -24,8 +25,16 @@ One JSON line:
   * bn_us: at B = 256, K = --filters, S = 19 the column and the channel form of the train-forward
     statistics, the BN + ReLU apply, the backward coefficients and the backward apply with the
     residual, each pair alternating in this process (``spread`` as above);
+  * wino_bn_us[B] for B = 256 and 512 at K = 128, S = 19: the fused-BN Winograd forward forms
+    with bias and residual -- the column form, the channel form without and with the next BN's
+    statistics -- and the unfused channel sequence the channel form replaces (bn_ch_apply into a
+    stored U + the direct 3x3 kernel), alternating in this process (``spread`` as above);
   * search_sims_per_s: ParallelMCTS(net, None) at mcts_bench.py --moves 6 --dual's geometry
-    (8192 playouts, waves of 512, lambda 0.5, GPU rollouts, from the empty board).
+    (8192 playouts, waves of 512, lambda 0.5, GPU rollouts, from the empty board);
+  * with --bn-axis 1, resdual_step_ch_wino_positions_per_s and search_ch_wino_sims_per_s: the
+    step and the search with the channel Winograd forward (ResTrunk.CH_WINO) ``on`` and ``off``
+    in this process, taking turns (medians; ``spread`` the largest max - min over a setting's
+    rounds).
 """
 import argparse
 import json
@@ -147,6 +156,63 @@ def bn_kernels(K, dev, B=256, S=19):
     return res_us
 
 
+def wino_bn_kernels(dev, K=128, S=19):
+    """us per call at B = 256 and 512 of the fused-BN Winograd forward forms on the same
+    activations and weights (conv_wino.hip): the column form (BNM 1), the channel form (BNM 3)
+    without and with the next BN's statistics, and the unfused channel sequence the channel form
+    replaces (bn_ch_apply into a stored U + the direct 3x3 kernel), every one with bias and
+    residual. The candidates alternate in this process."""
+    out = {}
+    g = torch.Generator(device=dev)
+    g.manual_seed(3)
+    w = torch.randn(K, K, 3, 3, device=dev, generator=g) * 0.05
+    b = torch.randn(K, device=dev, generator=g) * 0.1
+    uf, _ = ops.wino_weights(w, K, K, dgrad=False)
+    wf, _ = ops.pack_weights(w, K, K)
+    col = torch.zeros(3, S, device=dev)
+    col[0] = torch.rand(S, device=dev, generator=g) + 0.5
+    col[2] = torch.randn(S, device=dev, generator=g) * 0.3
+    ch = torch.zeros(3, K, device=dev)
+    ch[0] = torch.rand(K, device=dev, generator=g) + 0.5
+    ch[2] = torch.randn(K, device=dev, generator=g) * 0.3
+    for B in (256, 512):
+        assert ops.conv_wino_bn_ok(B, S, K, K), B
+        x, r = (ops.pack_nchw(torch.randn(B, K, S, S, device=dev, generator=g), 1, K)
+                for _ in range(2))
+        y, U = ops.alloc_padded(B, S, 1, K, dev), ops.alloc_padded(B, S, 1, K, dev)
+        part = torch.zeros(B, 2, K, device=dev)
+
+        def fused(coef, B=B, x=x, r=r, y=y, **kw):
+            return lambda: ops.conv_wino_bn(x, uf, b, y, B, S, K, K, False, bn_coef=coef,
+                                            residual=r, **kw)
+
+        def unfused(B=B, x=x, r=r, y=y, U=U):
+            ops.bn_ch_apply(x, U, B, S, K, coef=ch, relu=True)
+            ops.conv_igemm(U, wf, b, y, B, S, 1, 1, K, K, 3, False, residual=r)
+
+        out[str(B)] = alternate_with_spread({
+            "column_fwd": fused(col),
+            "channel_fwd": fused(ch, bn_axis=1),
+            "channel_fwd_stats": fused(ch, bn_axis=1, stat_part=part),
+            "channel_apply_plus_direct": unfused,
+        })
+    return out
+
+
+def ab_rates(make, rate, rounds=3):
+    """{"on": .., "off": .., "spread": ..}: ``rate(make(switch))`` with ResTrunk.CH_WINO on and
+    off, both built once and measured in alternating rounds in this process; the medians and the
+    largest max - min over a setting's rounds."""
+    cands = {"on": make(True), "off": make(False)}
+    runs = {k: [] for k in cands}
+    for _ in range(rounds):
+        for k, c in cands.items():
+            runs[k].append(rate(c))
+    res = {k: round(statistics.median(v), 1) for k, v in runs.items()}
+    res["spread"] = round(max(max(v) - min(v) for v in runs.values()), 1)
+    return res
+
+
 def sl_steps(B, filters, layers, steps, warmup, dev, bn_axis=-1):
     from rocalphago_amd.features.preprocessing import DEFAULT_FEATURES, VALUE_FEATURES
     from rocalphago_amd.models import kerasish as K
@@ -220,23 +286,54 @@ def sl_steps(B, filters, layers, steps, warmup, dev, bn_axis=-1):
     trp = SupervisedTrainer(pol, dsp, B, TRANSFORM_NAMES, None, seed=1, targets="visits")
     assert trp.plan is not None, "HIP fused plan not active"
     out["resnet_policy_step_positions_per_s"] = rate(trp.step)
+    del trp, pol
+
+    if bn_axis == 1:
+        # the channel Winograd forward (ResTrunk.CH_WINO) on and off: two trainers of the same
+        # network, alternating rounds in this process
+        def dual_trainer(switch):
+            saved = ResTrunk.CH_WINO
+            ResTrunk.CH_WINO = switch
+            try:
+                dual = ResnetPolicyValue(VALUE_FEATURES, **kw).model
+                dual.compile(loss=["categorical_crossentropy", "mse"],
+                             optimizer=K.SGD(lr=0.003), metrics=["accuracy"])
+                tr = PolicyValueTrainer(dual, ds, B, TRANSFORM_NAMES, None, seed=1,
+                                        targets="visits")
+            finally:
+                ResTrunk.CH_WINO = saved
+            assert tr.plan.trunk.bn_axis == 1
+            assert any(tr.plan.trunk._plan(B)[1]) == (switch and filters == 128)
+            return tr
+        out["resdual_step_ch_wino_positions_per_s"] = ab_rates(dual_trainer,
+                                                               lambda tr: rate(tr.step))
     return out
 
 
-def search(filters, layers, playouts, moves, dev, bn_axis=-1):
+def search(filters, layers, playouts, moves, dev, bn_axis=-1, ch_wino=None):
     """mcts_bench.measure's loop (it builds its own networks, so the loop is repeated here) on
-    a ParallelMCTS with the residual policy-value network."""
+    a ParallelMCTS with the residual policy-value network. ``ch_wino``: ResTrunk.CH_WINO while
+    the network's plan is built (None: as it stands)."""
     from rocalphago_amd.engine.gamestate import GameState
     from rocalphago_amd.features.preprocessing import DEFAULT_FEATURES
+    from rocalphago_amd.models.engine import ResTrunk
     from rocalphago_amd.models.policy_value import ResnetPolicyValue
     from rocalphago_amd.search.apv import ParallelMCTS
-    net = ResnetPolicyValue(DEFAULT_FEATURES + ["color"], board=19, filters_per_layer=filters,
-                            layers=layers, device=dev, seed=1, bn_axis=bn_axis)
-    mc = ParallelMCTS(net, None, lmbda=0.5, batch=512, rollout_device="gpu", rollouts_per_leaf=1,
-                      nthreads=16, seed=1, pipeline=3, max_inflight=8, rollout_group=8)
-    mc.n_playout = playouts
-    st = GameState()
-    mc.search(st, 512)  # compiles / allocates; discarded tree
+    saved = ResTrunk.CH_WINO
+    if ch_wino is not None:
+        ResTrunk.CH_WINO = ch_wino
+    try:
+        net = ResnetPolicyValue(DEFAULT_FEATURES + ["color"], board=19,
+                                filters_per_layer=filters, layers=layers, device=dev, seed=1,
+                                bn_axis=bn_axis)
+        mc = ParallelMCTS(net, None, lmbda=0.5, batch=512, rollout_device="gpu",
+                          rollouts_per_leaf=1, nthreads=16, seed=1, pipeline=3, max_inflight=8,
+                          rollout_group=8)
+        mc.n_playout = playouts
+        st = GameState()
+        mc.search(st, 512)  # compiles / allocates (builds the plan); discarded tree
+    finally:
+        ResTrunk.CH_WINO = saved
     mc._search = None
     mc.stats = {"waves": 0, "sims": 0}
     torch.cuda.synchronize()
@@ -272,12 +369,23 @@ def main():
     if not args.skip_heads:
         res["head_us"] = {str(B): head_kernels(B, args.filters, dev) for B in (256, 512)}
     res["bn_us"] = bn_kernels(args.filters, dev)
+    res["wino_bn_us"] = wino_bn_kernels(dev)
     if not args.skip_steps:
         res.update(sl_steps(args.batch, args.filters, args.layers, args.steps, args.warmup, dev,
                             args.bn_axis))
     if not args.skip_search:
         res.update(search(args.filters, args.layers, args.playouts, args.moves, dev,
                           args.bn_axis))
+        if args.bn_axis == 1:
+            # the channel Winograd forward on and off, a fresh search each, taking turns
+            runs = {"on": [], "off": []}
+            for _ in range(2):
+                for k in runs:
+                    runs[k].append(search(args.filters, args.layers, args.playouts, args.moves,
+                                          dev, 1, ch_wino=k == "on")["search_sims_per_s"])
+            ab = {k: round(statistics.median(v), 1) for k, v in runs.items()}
+            ab["spread"] = round(max(max(v) - min(v) for v in runs.values()), 1)
+            res["search_ch_wino_sims_per_s"] = ab
     print(json.dumps(res))
 
 

@@ -571,6 +571,20 @@ RAG_API int rag_bn_ch_train_fwd(const void* X, int hx, int B, int S, int C, int 
   return (int)hipGetLastError();
 }
 
+// rag_bn_ch_train_fwd's second half from per-block partials [nblk][2][CP] that another kernel
+// produced (the channel form of the Winograd conv epilogue, conv_wino.hip BNM 3: one row pair per
+// board): stats / coef / running averages, the partials summed in double.
+RAG_API int rag_bn_ch_finalize_fwd(const float* part, int nblk, int B, int S, int C, int CP,
+                                   const float* gamma, const float* beta, float* rmean,
+                                   float* rvar, float eps, float momentum, float* stats,
+                                   float* coef, hipStream_t stream) {
+  if (!ch_shape_ok(B, S, C, CP) || !part || nblk <= 0) return -1;
+  const BNArgs a{(double)B * S * S, eps, momentum, gamma, beta, rmean, rvar, stats, coef,
+                 nullptr, nullptr};
+  bn_finalize_kernel<0><<<CP, kT, 0, stream>>>(part, nblk, CP, C, a);
+  return (int)hipGetLastError();
+}
+
 RAG_API int rag_bn_ch_infer_coef(const float* gamma, const float* beta, float* rmean, float* rvar,
                                  float eps, int C, int CP, float* coef, hipStream_t stream) {
   if (C <= 0 || C > CP || CP % 8) return -1;

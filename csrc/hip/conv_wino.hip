@@ -167,12 +167,70 @@ __device__ __forceinline__ void vsumdiff_bn(const bf16x8& a, const bf16x8& b, fl
   d = __builtin_bit_cast(bf16x8, od);
 }
 
+// The channel form of the BN prologue (BNM 3): a raw value's coefficients belong to its channel
+// (cx[e], cc[e] of the thread's 8-channel slice), and a pixel outside the board must still give
+// U = 0, not ReLU(cc). U = med3(cx x + cc, 0, lim) with lim = FLT_MAX on a board pixel and 0
+// elsewhere: the ReLU and the halo select in the one instruction the column form spends on its
+// fmaxf.
+__device__ __forceinline__ float bn_ch_u(float cx, float x, float cc, float lim) {
+  return __builtin_amdgcn_fmed3f(fmaf(cx, x, cc), 0.f, lim);
+}
+template <int SGN>
+__device__ __forceinline__ bf16x8 vaddsub_ch(const bf16x8& a, const bf16x8& b,
+                                             const float (&cx)[8], const float (&cc)[8],
+                                             float la, float lb) {
+  const u32x4 ua = __builtin_bit_cast(u32x4, a), ub = __builtin_bit_cast(u32x4, b);
+  u32x4 o;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    const float a0 = bn_ch_u(cx[2 * w], __uint_as_float(ua[w] << 16), cc[2 * w], la);
+    const float a1 = bn_ch_u(cx[2 * w + 1], __uint_as_float(ua[w] & 0xffff0000u), cc[2 * w + 1], la);
+    const float b0 = bn_ch_u(cx[2 * w], __uint_as_float(ub[w] << 16), cc[2 * w], lb);
+    const float b1 = bn_ch_u(cx[2 * w + 1], __uint_as_float(ub[w] & 0xffff0000u), cc[2 * w + 1], lb);
+    const bf16x2 r = {(bf16)(SGN > 0 ? a0 + b0 : a0 - b0), (bf16)(SGN > 0 ? a1 + b1 : a1 - b1)};
+    o[w] = __builtin_bit_cast(uint32_t, r);
+  }
+  return __builtin_bit_cast(bf16x8, o);
+}
+__device__ __forceinline__ void vsumdiff_ch(const bf16x8& a, const bf16x8& b, const float (&cx)[8],
+                                            const float (&cc)[8], float la, float lb, bf16x8& s,
+                                            bf16x8& d) {
+  const u32x4 ua = __builtin_bit_cast(u32x4, a), ub = __builtin_bit_cast(u32x4, b);
+  u32x4 os, od;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    const float a0 = bn_ch_u(cx[2 * w], __uint_as_float(ua[w] << 16), cc[2 * w], la);
+    const float a1 = bn_ch_u(cx[2 * w + 1], __uint_as_float(ua[w] & 0xffff0000u), cc[2 * w + 1], la);
+    const float b0 = bn_ch_u(cx[2 * w], __uint_as_float(ub[w] << 16), cc[2 * w], lb);
+    const float b1 = bn_ch_u(cx[2 * w + 1], __uint_as_float(ub[w] & 0xffff0000u), cc[2 * w + 1], lb);
+    const bf16x2 rs = {(bf16)(a0 + b0), (bf16)(a1 + b1)}, rd = {(bf16)(b0 - a0), (bf16)(b1 - a1)};
+    os[w] = __builtin_bit_cast(uint32_t, rs);
+    od[w] = __builtin_bit_cast(uint32_t, rd);
+  }
+  s = __builtin_bit_cast(bf16x8, os);
+  d = __builtin_bit_cast(bf16x8, od);
+}
+
+// LDS past the loop ring / epilogue image of the channel form, in floats: the coefficient table
+// [2][128] (cx, cc) and the epilogue's per-wave channel sums [8 waves][2][128]
+constexpr int kChCP = 128;
+constexpr int kChTab = 2 * kChCP;
+constexpr int kChTail = kChTab + 8 * 2 * kChCP;
+
 // Fused BatchNorm of the 128-channel residual trunk (BNM template argument of conv_wino_kernel):
 //   BNM 1 (forward): X is the BN input x, the layer input U = ReLU(coef[0][col] x + coef[2][col])
 //          is built in the transform (never stored); `res` (or null) is added to the output; with
 //          spart, the block's (sum y, sum y^2) per board column of the stored output;
 //   BNM 2 (dgrad): the ReLU mask of U is recomputed from mask = x and coef; with spart,
-//          (sum dU, sum dU (x - smean)) per column of the masked output.
+//          (sum dU, sum dU (x - smean)) per column of the masked output;
+//   BNM 3 (forward, channel BN, ResTrunk bn_axis=1): as BNM 1 with one coefficient pair per
+//          CHANNEL, coef [3][128] (row 0 multiplies x, row 2 is the constant). A thread's
+//          transform units all load the same 8-channel slice of a chunk: 8 cx + 8 cc in registers,
+//          reloaded once per chunk-phase from an LDS copy of the table; halo pixels, the raw row
+//          past the last board and a missing unit give U = 0 through a per-raw-pixel limit
+//          (bn_ch_u). With spart, (sum y, sum y^2) per channel of the stored output as
+//          [gridDim.x][2][128], reduced in a fixed order (no float atomics: the same bits on
+//          every run).
 // spart: [gridDim.x][2][S] fp32 partials (one row pair per block = per board) for bn.hip's
 // finalize, as conv_tap_pp_kernel's BNP / mcoef / spart forms on the direct kernel.
 struct WinoBN {
@@ -321,7 +379,7 @@ __device__ __forceinline__ WinoGeom<SINGLE, WinoTile<WN, PAIRS>::MT> wino_geom(i
 }
 
 // One layer of a block: V transform, the two GEMM phases, epilogue. `lds`: T::Lds bf16 (+ the
-// BN forms' [2][64] float column accumulator past them).
+// BN forms' [2][64] float column accumulator past them; BNM 3: kChTail floats).
 // CHAIN (conv_wino_chain_kernel): no prologue warming of its own weights (the previous layer
 // did it); instead the L2-warming loads of `Unext` (the next layer's weights, or any valid
 // weights after the last layer) go out before the epilogue, whose LDS image and stores hide them.
@@ -376,6 +434,39 @@ __device__ __forceinline__ void wino_layer(
         const bool in = rin && pc >= 1 && pc <= S;
         bcx[q][s] = in ? bn.coef[pc - 1] : 0.f;
         bcc[q][s] = in ? bn.coef[2 * S + pc - 1] : 0.f;
+      }
+    }
+  }
+  // BNM 3: per transform unit, the limit of its four raw pixels d0..d3 (bn_ch_u: FLT_MAX on the
+  // board, 0 on the halo, past the last board and for a missing unit), and the coefficients of
+  // the 8-channel slice (the same for both units: unit u = threadIdx.x + 512 it, slice u & 3) of
+  // the chunk whose V is being built, read from the block's LDS table (conv_wino_kernel)
+  float blim[2][4], ccx[8], ccc[8];
+  auto load_coef = [&](int c) {
+    if constexpr (BNM == 3) {
+      const float* tab = reinterpret_cast<const float*>(lds + T::Lds) + c * kWK +
+                         (threadIdx.x & 3) * 8;
+      const float4 x0 = *reinterpret_cast<const float4*>(tab);
+      const float4 x1 = *reinterpret_cast<const float4*>(tab + 4);
+      const float4 c0 = *reinterpret_cast<const float4*>(tab + kChCP);
+      const float4 c1 = *reinterpret_cast<const float4*>(tab + kChCP + 4);
+      ccx[0] = x0.x, ccx[1] = x0.y, ccx[2] = x0.z, ccx[3] = x0.w;
+      ccx[4] = x1.x, ccx[5] = x1.y, ccx[6] = x1.z, ccx[7] = x1.w;
+      ccc[0] = c0.x, ccc[1] = c0.y, ccc[2] = c0.z, ccc[3] = c0.w;
+      ccc[4] = c1.x, ccc[5] = c1.y, ccc[6] = c1.z, ccc[7] = c1.w;
+    }
+  };
+  if constexpr (BNM == 3) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int pk = q ? tu1 : tu0;
+      const int v = pk < 0 ? 0 : (pk & 1023);
+      const int r = v / TJ, t = v - r * TJ;  // padded row r, pair column t (one board)
+      const bool rin = pk >= 0 && r >= 1 && r <= S;
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        const int pc = 2 * t + s;  // padded column of d_s
+        blim[q][s] = rin && pc >= 1 && pc <= S ? __FLT_MAX__ : 0.f;
       }
     }
   }
@@ -440,6 +531,8 @@ __device__ __forceinline__ void wino_layer(
       bf16x8 vs1, vs2;
       if constexpr (BNM == 1)
         vsumdiff_bn(da, db, bcx[u][ra], bcc[u][ra], bcx[u][rb], bcc[u][rb], vs1, vs2);
+      else if constexpr (BNM == 3)
+        vsumdiff_ch(da, db, ccx, ccc, blim[u][ra], blim[u][rb], vs1, vs2);
       else
         vsumdiff(da, db, vs1, vs2);
       *reinterpret_cast<bf16x8*>(vs) = vs1;
@@ -448,6 +541,8 @@ __device__ __forceinline__ void wino_layer(
       bf16x8 val;
       if constexpr (BNM == 1)
         val = vaddsub_bn<-1>(da, db, bcx[u][ra], bcc[u][ra], bcx[u][rb], bcc[u][rb]);
+      else if constexpr (BNM == 3)
+        val = vaddsub_ch<-1>(da, db, ccx, ccc, blim[u][ra], blim[u][rb]);
       else
         val = vdiff(da, db);
       *reinterpret_cast<bf16x8*>(vs + h * kVSlot * 2) = val;
@@ -512,6 +607,7 @@ __device__ __forceinline__ void wino_layer(
     wA[j] = wfrag(1, 0, j);
     wB[j] = wfrag(2, 0, j);
   }
+  load_coef(0);
   op_load(IntC<1>{}, 0, IntC<0>{});  // V(0) (phase 1)
   op_store(IntC<1>{}, IntC<0>{});
   if constexpr (kUnits == 2) {
@@ -589,6 +685,7 @@ __device__ __forceinline__ void wino_layer(
       }
       __builtin_amdgcn_sched_barrier(0);
     };
+    load_coef(cn);  // every transform store of this chunk-phase (slots 2..5) builds chunk cn's V
     step(IntC<0>{});
     step(IntC<1>{});
     step(IntC<2>{});
@@ -654,6 +751,13 @@ __device__ __forceinline__ void wino_layer(
     constexpr int kChunks = kWN / 8;
     const int total = S2 * kChunks, nit = (total + 511) / 512;
     const bool st = bn.spart != nullptr;
+    // BNM 3: a thread's 16-byte chunk of a pixel row is threadIdx.x % 16 on every pass (512 is a
+    // multiple of 16), so its running sums always belong to the same 8 channels
+    float cs0[8], cs1[8];
+    if constexpr (BNM == 3) {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) cs0[q] = cs1[q] = 0.f;
+    }
     for (int it = 0; it < nit; ++it) {
       const int e = threadIdx.x + it * 512;
       const bool valid = e < total;
@@ -664,17 +768,26 @@ __device__ __forceinline__ void wino_layer(
         const int m = i * TJ + (j >> 1);
         bf16x8 v = *reinterpret_cast<const bf16x8*>(lds + (2 * m + (j & 1)) * kEpRow + k8);
         const size_t yo = (size_t)((b0 * WO + i + HO) * WO + j + HO) * YC + n0 + k8;
-        if constexpr (BNM == 1) {
+        if constexpr (BNM == 1 || BNM == 3) {
           if (bn.res) {  // the residual unit's skip (bias (+ ReLU) already in the image)
             const bf16x8 r = *reinterpret_cast<const bf16x8*>(bn.res + yo);
 #pragma unroll
             for (int q = 0; q < 8; ++q) v[q] = (bf16)((float)v[q] + (float)r[q]);
           }
+          if constexpr (BNM == 1) {
 #pragma unroll
-          for (int q = 0; q < 8; ++q) {
-            const float f = (float)v[q];
-            s0 += f;
-            s1 = fmaf(f, f, s1);
+            for (int q = 0; q < 8; ++q) {
+              const float f = (float)v[q];
+              s0 += f;
+              s1 = fmaf(f, f, s1);
+            }
+          } else if (st) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+              const float f = (float)v[q];
+              cs0[q] += f;
+              cs1[q] = fmaf(f, f, cs1[q]);
+            }
           }
         } else {
           const bf16x8 mk = *reinterpret_cast<const bf16x8*>(
@@ -692,19 +805,51 @@ __device__ __forceinline__ void wino_layer(
         }
         *reinterpret_cast<bf16x8*>(Y + yo) = v;
       }
-      if (st) {
+      if constexpr (BNM != 3) {
+        if (st) {
 #pragma unroll
-        for (int o = kChunks / 2; o > 0; o >>= 1) {
-          s0 += __shfl_xor(s0, o, 64);
-          s1 += __shfl_xor(s1, o, 64);
-        }
-        if ((threadIdx.x & (kChunks - 1)) == 0 && valid) {
-          atomicAdd(sred + j, s0);
-          atomicAdd(sred + 64 + j, s1);
+          for (int o = kChunks / 2; o > 0; o >>= 1) {
+            s0 += __shfl_xor(s0, o, 64);
+            s1 += __shfl_xor(s1, o, 64);
+          }
+          if ((threadIdx.x & (kChunks - 1)) == 0 && valid) {
+            atomicAdd(sred + j, s0);
+            atomicAdd(sred + 64 + j, s1);
+          }
         }
       }
     }
-    if (st) {
+    if constexpr (BNM == 3) {
+      // channel sums in a fixed order: the 4 lanes of a wave that share a chunk (lane, lane ^ 16,
+      // lane ^ 32, lane ^ 48) by shuffles, then the 8 waves through LDS in wave order
+      if (st) {
+        static_assert(kChunks == 16 && kWN == kChCP, "channel statistics: 16 chunks per pixel");
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          cs0[q] += __shfl_xor(cs0[q], 16, 64);
+          cs1[q] += __shfl_xor(cs1[q], 16, 64);
+          cs0[q] += __shfl_xor(cs0[q], 32, 64);
+          cs1[q] += __shfl_xor(cs1[q], 32, 64);
+        }
+        float* wsum = reinterpret_cast<float*>(lds + T::Lds) + kChTab;
+        if (lane < 16) {
+          float* w0 = wsum + (wave_id() * 2) * kChCP + lane * 8;
+#pragma unroll
+          for (int q = 0; q < 8; ++q) {
+            w0[q] = cs0[q];
+            w0[kChCP + q] = cs1[q];
+          }
+        }
+        __syncthreads();
+        if (threadIdx.x < 2 * kChCP) {
+          const int q = threadIdx.x / kChCP, c = threadIdx.x - q * kChCP;
+          float s = 0.f;
+#pragma unroll
+          for (int w = 0; w < 8; ++w) s += wsum[(w * 2 + q) * kChCP + c];
+          bn.spart[((size_t)blockIdx.x * 2 + q) * kChCP + c] = s;
+        }
+      }
+    } else if (st) {
       __syncthreads();
       if ((int)threadIdx.x < 2 * S) {
         const int q = threadIdx.x / S, c = threadIdx.x - q * S;
@@ -746,8 +891,18 @@ conv_wino_kernel(const bf16* __restrict__ X, const bf16* __restrict__ U,
                  int relu, int HM, int nb, WgradRed red, WinoBN bn = WinoBN{}) {
   using T = WinoTile<WN, PAIRS>;
   // + a [2][64] float column-statistics accumulator past the loop ring / epilogue image
-  __shared__ __attribute__((aligned(16))) bf16 lds[T::Lds + (BNM ? 256 : 0)];
-  if constexpr (BNM != 0) {
+  // (the channel form: its coefficient table and per-wave channel sums, kChTail floats)
+  constexpr int kTail = BNM == 3 ? 2 * kChTail : (BNM ? 256 : 0);
+  static_assert((T::Lds + kTail) * 2 <= 160 * 1024, "LDS budget");
+  __shared__ __attribute__((aligned(16))) bf16 lds[T::Lds + kTail];
+  if constexpr (BNM == 3) {
+    // rows 0 (cx) and 2 (cc) of coef [3][128] -> the LDS table every chunk-phase reads its
+    // slice from (wino_layer load_coef; the first read is V(0)'s, hence the barrier here)
+    float* tab = reinterpret_cast<float*>(lds + T::Lds);
+    if (threadIdx.x < kChTab)
+      tab[threadIdx.x] = bn.coef[(threadIdx.x / kChCP) * 2 * kChCP + threadIdx.x % kChCP];
+    __syncthreads();
+  } else if constexpr (BNM != 0) {
     float* sred = reinterpret_cast<float*>(lds + T::Lds);
     if (bn.spart && threadIdx.x < 128) sred[threadIdx.x] = 0.f;  // published by the first barrier
   }
@@ -1011,6 +1166,23 @@ int rag_conv_wino_bn_launch(const void* X, const void* W, const float* bias, voi
     conv_wino_kernel<128, true, kWP, 2><<<B, 512, 0, stream>>>(
         (const bf16*)X, (const bf16*)W, bias, (bf16*)Y, (const bf16*)mask, B, S, KIN, NOUT, HO,
         YC, relu, HM, 1, r, WinoBN{mcoef, nullptr, spart, smean});
+  return (int)hipGetLastError();
+}
+
+// The channel-BN forward form (BNM 3, ResTrunk bn_axis=1): X = the BN input x (halo 1), the layer
+// input U = ReLU(coef[0][c] x + coef[2][c]) built in the transform, coef [3][128] fp32; `resid`
+// (laid out like Y) optional; spart [B][2][128] optional: per-board (sum y, sum y^2) per channel of
+// the stored output for rag_bn_ch_finalize_fwd (nblk = B). Forward only: no mask, no pending
+// reduction. -5 when rag_conv_wino_bn_ok is false for the shape or coef is missing.
+RAG_API int rag_conv_wino_bn_ch(const void* X, const void* W, const float* bias, void* Y,
+                                const void* resid, int B, int S, int KIN, int NOUT, int HO, int YC,
+                                int relu, hipStream_t stream, const float* coef, float* spart) {
+  if (!wino_bn_ok(B, S, KIN, NOUT) || NOUT != kChCP || YC < NOUT || HO < 0 || !coef || !X ||
+      !W || !Y)
+    return -5;
+  conv_wino_kernel<128, true, kWP, 3><<<B, 512, 0, stream>>>(
+      (const bf16*)X, (const bf16*)W, bias, (bf16*)Y, nullptr, B, S, KIN, NOUT, HO, YC, relu, 1, 1,
+      WgradRed{}, WinoBN{coef, (const bf16*)resid, spart, nullptr});
   return (int)hipGetLastError();
 }
 

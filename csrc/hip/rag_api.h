@@ -50,6 +50,9 @@ RAG_API int rag_pack_nchw(const float* in, void* X, int B, int C, int S, int H, 
 RAG_API int rag_conv_wino_ok(int S, int HI, int KIN, int NOUT, int KS);
 RAG_API int rag_conv_wino_mode(int B, int S, int KIN, int NOUT);
 RAG_API int rag_conv_wino_bn_ok(int B, int S, int KIN, int NOUT);
+RAG_API int rag_conv_wino_bn_ch(const void* X, const void* W, const float* bias, void* Y,
+                                const void* resid, int B, int S, int KIN, int NOUT, int HO, int YC,
+                                int relu, hipStream_t stream, const float* coef, float* spart);
 RAG_API int rag_conv_wino_chain(const int64_t* table, int L, int B, int S, hipStream_t stream,
                                 int any_batch);
 RAG_API int rag_wino_pack(const int64_t* table, int nlayers, int max_tiles, hipStream_t stream,
@@ -171,6 +174,10 @@ RAG_API int rag_bn_ch_train_fwd(const void* X, int hx, int B, int S, int C, int 
                                 const float* gamma, const float* beta, float* rmean, float* rvar,
                                 float eps, float momentum, float* stats, float* coef, float* work,
                                 hipStream_t stream);
+RAG_API int rag_bn_ch_finalize_fwd(const float* part, int nblk, int B, int S, int C, int CP,
+                                   const float* gamma, const float* beta, float* rmean,
+                                   float* rvar, float eps, float momentum, float* stats,
+                                   float* coef, hipStream_t stream);
 RAG_API int rag_bn_ch_infer_coef(const float* gamma, const float* beta, float* rmean, float* rvar,
                                  float eps, int C, int CP, float* coef, hipStream_t stream);
 RAG_API int rag_bn_ch_bwd_coef(const void* X, int hx, const void* DY, int hd, int B, int S, int C,

@@ -478,16 +478,31 @@ class ResTrunk(_PackedConvs):
     at B=256, K=128) — trivial against 288 GB of HBM.
 
     ``bn_axis=1`` (one statistic per channel, the residual tower of He et al. / AlphaGo Zero;
-    the default -1 is the reference's column BN above): every BN runs the unfused sequence on
-    the channel kernels (bn.hip rag_bn_ch_*) -- statistics or running coefficients, one BN+ReLU
-    pass into U, the plain conv with the residual epilogue; backward wgrad, dgrad masked by U,
-    the channel backward reduction and one apply that adds the skip gradient. No BN prologue,
-    no Winograd BN kernel, and stats / coef hold one slot per padded channel."""
+    the default -1 is the reference's column BN above): the BNs run on the channel kernels
+    (bn.hip rag_bn_ch_*) and stats / coef hold one slot per padded channel. The general sequence
+    is unfused -- statistics or running coefficients, one BN+ReLU pass into U, the plain conv
+    with the residual epilogue; backward wgrad, dgrad masked by U, the channel backward
+    reduction and one apply that adds the skip gradient; no BN prologue in the direct kernels.
+    The forward of a 128-wide trunk's 3x3 layers (K == KP == 128, halo 1, batches with
+    ops.conv_wino_bn_ok; ``CH_WINO``) runs the channel form of the Winograd BN kernel instead
+    (conv_wino.hip BNM 3, ``_plan(B)[1]``): U = ReLU(cx[c] x + cc[c]) is built in the input
+    transform from the BN input, the residual is added in the epilogue, and in training the
+    epilogue also sums the next BN's channel statistics per board (bn_ch_finalize_fwd replaces
+    that BN's statistics pass). Inference then writes no U at all; the training forward still
+    stores U with bn_ch_apply, because the backward is unchanged: it runs the direct kernels on
+    the stored U (wgrad operand and dgrad mask), so ``_fused`` -- "U was never stored" -- stays
+    False for channel trunks. The Winograd forward builds U in fp32 and rounds once at V, while
+    the wgrad reads the bf16-rounded stored U: the two differ by that one rounding; the dgrad
+    mask U > 0 has the same sign either way."""
 
     # 3x3 128 -> 128 layers whose input BN is fused run the Winograd BN kernel: "0" off, "1"
     # forward only (default), "2" forward and dgrad (see __init__)
     WINO_MODE = "1"
     DEFER_REDUCE = True
+    # channel BN (bn_axis=1): the 3x3 layers of a 128-wide trunk run the channel form of the
+    # Winograd BN kernel forward (False: the unfused sequence on the direct kernel, the A/B);
+    # read when the trunk is built
+    CH_WINO = True
 
     def __init__(self, specs, units, bns, board, device, raw_top=False, bn_axis=-1):
         assert specs and len(specs) == 1 + sum(units) == 1 + len(bns)
@@ -521,10 +536,18 @@ class ResTrunk(_PackedConvs):
         # (51.6 vs 48.6 us on the direct kernel; standalone it is 37.4 us + a 16.6 us reduction,
         # and riding in the BN backward apply made that pass 47.9 instead of 18.5 us). ResNet
         # 71.6 k (1) / 70.9 k (2) / 69.7 k (2, no deferral) / 68.0 k (0) positions/s on one box.
-        # (channel BN has no fused kernel: no Winograd layers, no packing tables for them)
+        # Channel BN: the forward-only channel form (conv_wino.hip BNM 3) for a trunk of exactly
+        # 128 unpadded channels (CH_WINO); no dgrad form, no prologue in the direct kernels.
         mode = str(self.WINO_MODE) if device.type == "cuda" and bn_axis != 1 else "0"
-        wino = [mode != "0" and l > 0 and s.ks == 3 and s.cinp == s.coutp == 128
-                and ops.conv_wino_ok(board, 1, s.cinp, s.coutp, 3) for l, s in enumerate(specs)]
+        if bn_axis == 1:
+            on = bool(self.CH_WINO) and device.type == "cuda" and K == self.KP == 128
+            wino = [on and l > 0 and s.ks == 3 and s.cinp == s.coutp == 128
+                    and ops.conv_wino_ok(board, 1, s.cinp, s.coutp, 3)
+                    for l, s in enumerate(specs)]
+        else:
+            wino = [mode != "0" and l > 0 and s.ks == 3 and s.cinp == s.coutp == 128
+                    and ops.conv_wino_ok(board, 1, s.cinp, s.coutp, 3)
+                    for l, s in enumerate(specs)]
         self._init_packing(specs, device, wino)
         self.wino_dgrad = mode == "2"
         self._wino_plans = {}
@@ -575,8 +598,12 @@ class ResTrunk(_PackedConvs):
         self.stats = torch.zeros((nb, 2, n), dtype=torch.float32, device=dev)
         self.coef = torch.zeros((nb, 3, n), dtype=torch.float32, device=dev)
         self.bcoef = torch.zeros((3, n), dtype=torch.float32, device=dev)
-        if self.bn_axis == 1:  # nothing fused: no conv epilogue writes statistics
-            self.spart = self.bpart = None
+        if self.bn_axis == 1:
+            # the channel Winograd forward writes one partial row pair per board and BN; the
+            # backward is unfused: no conv epilogue writes its statistics
+            self.spart = torch.zeros((nb, B, 2, KP), dtype=torch.float32, device=dev) \
+                if any(self._wino) else None
+            self.bpart = None
         else:
             # BN column-statistics partials written by the fused conv epilogues (forward: one
             # per BN, whose input that conv produced; backward: one, reused layer by layer)
@@ -619,8 +646,14 @@ class ResTrunk(_PackedConvs):
 
     def _plan(self, B):
         """(fused, wino) at batch B: per BN j, fused into conv j+1's prologue; per conv l, runs
-        the Winograd BN kernel (its input BN fused, a grid that fills the chip)."""
+        the Winograd BN kernel (its input BN fused, a grid that fills the chip). Channel trunks:
+        nothing is fused (U is stored in training), and conv l's FORWARD runs the channel form
+        of the Winograd BN kernel."""
         plan = self._wino_plans.get(B)
+        if plan is None and self.bn_axis == 1:
+            ok = any(self._wino) and ops.conv_wino_bn_ok(B, self.S, self.KP, self.KP)
+            plan = self._wino_plans[B] = ([False] * len(self.bns),
+                                          [bool(w and ok) for w in self._wino])
         if plan is None:
             fused = [self._prologue_ok(j, B) for j in range(len(self.bns))]
             wino = [w and l > 0 and fused[l - 1] and ops.conv_wino_bn_ok(B, self.S, self.KP,
@@ -651,7 +684,11 @@ class ResTrunk(_PackedConvs):
         for u, n in enumerate(self.units):
             for i in range(n):
                 bn, x, U = self.bns[j], self._bn_input(j, u, B), self.U[j][:B]
-                if training and stat_ready[j]:
+                if training and stat_ready[j] and ch:  # one partial row pair per board
+                    ops.bn_ch_finalize_fwd(self.spart[j], B, B, S, K, bn.gamma, bn.beta,
+                                           bn.rmean, bn.rvar, bn.eps, bn.momentum,
+                                           self.stats[j], self.coef[j])
+                elif training and stat_ready[j]:
                     ops.bn_finalize_fwd(self.spart[j], self._stat_blocks(j, B), B, S, K,
                                         bn.gamma, bn.beta,
                                         bn.rmean, bn.rvar, bn.eps, bn.momentum, self.stats[j],
@@ -681,6 +718,17 @@ class ResTrunk(_PackedConvs):
                         ops.conv_igemm_bn(x, self._wf[l], self._bias[l], y, B, S, sp.cinp,
                                           sp.coutp, False, bn_coef=self.coef[j], residual=res,
                                           stat_part=sp_out)
+                    if sp_out is not None:
+                        stat_ready[l] = True
+                elif ch and wino[l]:
+                    # the channel form builds U from x in its transform; the stored U is the
+                    # unfused backward's (wgrad operand, dgrad mask), inference writes none
+                    if training:
+                        ops.bn_ch_apply(x, U, B, S, K, coef=self.coef[j], relu=True)
+                    sp_out = self.spart[l] if training and l < nb else None
+                    ops.conv_wino_bn(x, self._uf[l], self._bias[l], y, B, S, sp.cinp, sp.coutp,
+                                     False, bn_coef=self.coef[j], residual=res,
+                                     stat_part=sp_out, bn_axis=1)
                     if sp_out is not None:
                         stat_ready[l] = True
                 else:

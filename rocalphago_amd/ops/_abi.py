@@ -29,6 +29,7 @@ SIGNATURES = {
     "rag_conv_wino_mode": [I, I, I, I],
     "rag_conv_wino_bn_ok": [I, I, I, I],
     "rag_conv_wino_bn": [P] * 6 + [I] * 8 + [P] * 6,
+    "rag_conv_wino_bn_ch": [P] * 5 + [I] * 7 + [P] * 3,
     "rag_conv_wino_chain": [P, I, I, I, P, I],
     "rag_pack_input_u8": [P, P, P, P, I, I, I, I, I, I, P],
     "rag_pack_input_f32": [P, P, P, P, I, I, I, I, I, I, P],
@@ -67,6 +68,7 @@ SIGNATURES = {
     "rag_bn_apply_bwd_part": [P, I, P, P, P, P, P, I, P, I, P, I, P, I, I, I, I, I, P],
     "rag_bn_finalize_fwd": [P, I, I, I, I, P, P, P, P, F, F, P, P, P],
     "rag_bn_finalize_bwd": [P, I, I, I, I, P, P, P, P, P, P],
+    "rag_bn_ch_finalize_fwd": [P, I, I, I, I, I, P, P, P, P, F, F, P, P, P],
     "rag_bn_ch_workspace": [I, I, I],
     "rag_bn_ch_train_fwd": [P, I, I, I, I, I, P, P, P, P, F, F, P, P, P, P],
     "rag_bn_ch_infer_coef": [P, P, P, P, F, I, I, P, P],

@@ -269,17 +269,50 @@ def conv_wino_bn_ok(B, S, kin, nout):
 
 
 def conv_wino_bn(x, u, bias, y, B, S, kin, nout, relu, bn_coef=None, mask=None, mask_coef=None,
-                 residual=None, pending=None, stat_part=None, stat_mean=None):
+                 residual=None, pending=None, stat_part=None, stat_mean=None, bn_axis=-1):
     """conv_igemm_bn's two forms on the Winograd kernel (conv_wino.hip WinoBN) with the layer's
     Winograd weights ``u``: forward (``bn_coef``: x is the BN input, U = ReLU(bn_coef[0][col] x +
     bn_coef[2][col]) is built in the input transform; optional ``residual``) or dgrad
     (``mask`` = x and ``mask_coef``). ``stat_part`` [B, 2, S]: one partial row pair per board
-    (bn_finalize_fwd / bn_finalize_bwd with nblk = B). Needs conv_wino_bn_ok(B, ...)."""
+    (bn_finalize_fwd / bn_finalize_bwd with nblk = B). Needs conv_wino_bn_ok(B, ...).
+
+    ``bn_axis=1``: the channel form, forward only. ``bn_coef`` [3, 128] holds one coefficient
+    pair per channel (U = ReLU(bn_coef[0][c] x + bn_coef[2][c])), ``stat_part`` [>= B, 2, 128]
+    receives per-board channel sums (sum y, sum y^2) for bn_ch_finalize_fwd with nblk = B, bit
+    for bit the same on every run."""
+    if bn_axis not in (-1, 1):
+        raise ValueError("conv_wino_bn: bn_axis must be -1 (column) or 1 (channel)")
+    slots = 128 if bn_axis == 1 else S
+    if bn_axis == 1:
+        if mask is not None or mask_coef is not None or stat_mean is not None \
+                or pending is not None:
+            raise ValueError("conv_wino_bn: the channel form (bn_axis=1) is forward only "
+                             "(no mask, mask_coef, stat_mean or pending)")
+        if bn_coef is None:
+            raise ValueError("conv_wino_bn: the channel form (bn_axis=1) needs bn_coef")
+        if kin != 128 or nout != 128:
+            raise ValueError("conv_wino_bn: the channel form runs 128 -> 128 channels")
+    if bn_coef is not None and (tuple(bn_coef.shape) != (3, slots)
+                                or bn_coef.dtype != torch.float32):
+        raise ValueError("conv_wino_bn: bn_coef must be fp32 [3, %d]" % slots)
+    if bn_axis == 1 and stat_part is not None and (
+            stat_part.dim() != 3 or stat_part.shape[0] < B
+            or tuple(stat_part.shape[1:]) != (2, 128) or stat_part.dtype != torch.float32):
+        raise ValueError("conv_wino_bn: stat_part must be fp32 [>= %d, 2, 128]" % B)
     _index_range_ok(x, y, mask, residual)
     if x.shape[1] != S + 2 or x.shape[-1] != kin or y.shape[1] != S + 2:
         raise ValueError("conv_wino_bn input and output have halo 1 (%d input channels)" % kin)
     if residual is not None and residual.shape[1:] != y.shape[1:]:
         raise ValueError("residual layout does not match the output")
+    if bn_axis == 1:
+        if y.shape[-1] < nout or not bn_coef.is_contiguous() or \
+                (stat_part is not None and not stat_part.is_contiguous()):
+            raise ValueError("conv_wino_bn: contiguous bn_coef / stat_part, %d output channels"
+                             % nout)
+        _check(_lib().rag_conv_wino_bn_ch(_ptr(x), _ptr(u), _ptr(bias), _ptr(y), _ptr(residual),
+                                          B, S, kin, nout, 1, y.shape[-1], int(relu), _stream(),
+                                          _ptr(bn_coef), _ptr(stat_part)), "conv_wino_bn")
+        return y
     if mask is not None and (mask.shape[1] != S + 2 or mask.shape[-1] != y.shape[-1]):
         raise ValueError("mask layout does not match (halo 1, %d channels)" % y.shape[-1])
     if (mask is None) != (mask_coef is None) or (bn_coef is None) == (mask_coef is None):
@@ -444,6 +477,23 @@ def bn_ch_train_fwd(x, B, S, C, gamma, beta, rmean, rvar, eps, momentum, stats, 
                                       float(momentum), _ptr(stats), _ptr(coef),
                                       _ptr(bn_ch_workspace(B, S, CP, x.device)), _stream()),
            "bn_ch_train_fwd")
+
+
+def bn_ch_finalize_fwd(part, nblk, B, S, C, gamma, beta, rmean, rvar, eps, momentum, stats, coef):
+    """bn_ch_train_fwd from per-block channel partials [>= nblk, 2, CP] that a fused conv epilogue
+    wrote (conv_wino_bn(bn_axis=1) ``stat_part``: nblk = B): the channel twin of
+    bn_finalize_fwd, the same double-precision sum and running-average update as
+    bn_ch_train_fwd's second half."""
+    if part.dim() != 3 or part.shape[1] != 2 or part.shape[0] < nblk or nblk < 1 \
+            or part.dtype != torch.float32 or not part.is_contiguous():
+        raise ValueError("bn_ch_finalize_fwd: part must be contiguous fp32 [>= nblk, 2, CP]")
+    CP = part.shape[-1]
+    _ch_slots(stats, 2, CP, "bn_ch_finalize_fwd stats")
+    _ch_slots(coef, 3, CP, "bn_ch_finalize_fwd coef")
+    _check(_lib().rag_bn_ch_finalize_fwd(_ptr(part), int(nblk), B, S, C, CP, _ptr(gamma),
+                                         _ptr(beta), _ptr(rmean), _ptr(rvar), float(eps),
+                                         float(momentum), _ptr(stats), _ptr(coef), _stream()),
+           "bn_ch_finalize_fwd")
 
 
 def bn_ch_infer_coef(gamma, beta, rmean, rvar, eps, C, CP, coef):
